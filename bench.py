@@ -28,6 +28,20 @@ pinned host memory), `value_delivered` (copied in AND every result -- counts, ke
 landed in pinned host memory: gfo_batch_deliver), `per_frame_boundary` (the reference's own call pattern, one stereo
 frame per call from K host threads through the C ABI: tools/c/boundary_throughput.c) and `matcher_calls` (ms per call of the
 host-array matcher calls Tracking makes per frame: tools/matcher_call_latency.py).
+
+A plain run does only what the headline needs: setup (including the priming batches), --warmup, the --steps timed steps,
+the outputs of the last timed step if --dump-outputs DIR is given, and the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step and the run's configuration).  Everything else described above -- the oracle check of
+the last step, the roofline and its counter passes, the sustained / strong-scaling / H2D / delivered / latency figures, the
+other BASELINE configs, real_image, per_frame_boundary, matcher_calls and the CPU baseline -- runs only with --full.
+
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the batch path receives it, into DIR/<name>.npy
+(float32 / float64, under 64 MB in all): the keypoint count of every image, and keypoints, descriptors and the matcher's
+outputs of a fixed, seeded sample of the batch's units (stereo pairs for stereo752, images otherwise) -- see dump_outputs().
+The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import ctypes
@@ -228,7 +242,7 @@ def side_config(name, batch, streams):
     249k, proj1080 46.5k against 51.2k frames/s, measured both ways)."""
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", name, "--batch", str(batch), "--steps", "400", "--warmup", "30",
-           "--streams", str(streams), "--no-other-configs", "--no-cpu-baseline", "--no-boundary", "--no-live-traffic", "--profile-steps", "5"]   # (each verifies its own last step)
+           "--streams", str(streams), "--full", "--no-other-configs", "--no-cpu-baseline", "--no-boundary", "--no-live-traffic", "--profile-steps", "5"]   # (each verifies its own last step)
     try:
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=240)
         lines = [l for l in r.stdout.decode(errors="replace").splitlines() if l.startswith("{")]
@@ -919,11 +933,99 @@ class Job:
             "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
             "all_kernels": per_stage}
 
+    def dump_outputs(self, out_dir, budget=60 << 20):
+        """What the LAST step submitted computed (still in that context's arena), as a caller of the batch path receives it
+        (gfo_batch_counts / gfo_batch_fetch / gfo_stereo_fetch / gfo_projection_fetch), into out_dir/<name>.npy.  Counts of every
+        image; keypoints, descriptors and matcher outputs of a fixed, seeded sample of the units (stereo pairs for a stereo
+        workload, images otherwise) sized from the context's keypoint capacity -- never from the counts, so two builds that
+        disagree still dump the same units -- to stay within `budget` bytes.  Call right after timed().  Returns a summary."""
+        self.torch.cuda.synchronize()
+        k = self.last_ctx
+        ext, m = self.exts[k], self.matchers[k]
+        B, cap = self.B, ext.max_keypoints()
+        per_unit_img = 2 if self.matcher == "stereo" else 1
+        units = B // per_unit_img
+        # bytes per unit at full capacity: keypoints (7 x f32) + descriptors (32 x f32) per image, matcher columns per keypoint
+        unit_bytes = per_unit_img * cap * (7 + 32) * 4 + cap * 4 * {"stereo": 4, "project": 2}.get(self.matcher, 0)
+        n_s = int(max(1, min(units, (budget - 8 * (B + units + 2 * B)) // unit_bytes)))
+        sample = np.sort(np.random.default_rng(20261016).permutation(units)[:n_s])
+        images = np.concatenate([np.arange(u * per_unit_img, (u + 1) * per_unit_img) for u in sample])
+        out = {"counts": ext.batch_counts(B).astype(np.float64), "sample_images": images.astype(np.float64)}
+        kps, descs, match, nmatched = [], [], [], []
+        for i in images:
+            kp, desc = ext.batch_fetch(int(i))
+            kps.append(np.stack([kp[f].astype(np.float32) for f in kp.dtype.names], axis=1) if len(kp) else np.zeros((0, 7), np.float32))
+            descs.append(desc.astype(np.float32))
+            if self.matcher == "stereo" and i % 2 == 0:
+                nm, u_r, depth, best_dist, best_idx = m.stereo_fetch(int(i) // 2, len(kp))
+                nmatched.append(nm)
+                match.append(np.stack([u_r, depth, best_dist.astype(np.float32), best_idx.astype(np.float32)], axis=1)[:len(kp)])
+            elif self.matcher == "project":
+                nm, out_mp, out_sc = m.projection_fetch(int(i), len(kp))
+                nmatched.append(nm)
+                match.append(np.stack([out_mp[:len(kp)].astype(np.float32), out_sc[:len(kp)].astype(np.float32)], axis=1))
+        # keypoint columns: x, y, size, angle, response, octave, class_id (KEYPOINT_DTYPE); rows: the sampled images in order
+        out["keypoints"] = np.concatenate(kps)
+        out["descriptors"] = np.concatenate(descs)
+        if self.matcher == "stereo":
+            # per left keypoint of every sampled pair: uRight, depth, best distance, best right index (gfo_stereo_fetch)
+            out["stereo_nmatched"] = np.asarray(nmatched, np.float64)
+            out["stereo_outputs"] = np.concatenate(match)
+        elif self.matcher == "project":
+            # per keypoint of every sampled frame: matched map point (-1 none), score (gfo_projection_fetch)
+            out["projection_nmatched"] = np.asarray(nmatched, np.float64)
+            out["projection_outputs"] = np.concatenate(match)
+        os.makedirs(out_dir, exist_ok=True)
+        total = 0
+        for name, a in out.items():
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            total += a.nbytes
+        assert total <= 64 << 20, f"dumped outputs are {total} bytes"
+        return {"dir": out_dir, "files": sorted(n + ".npy" for n in out), "bytes": int(total), "input_batch": int(self.last_in),
+                "context": int(k), "sampled_units": int(n_s), "units": int(units)}
+
     def close(self):
         for e in self.exts:
             e.close()
         self.d_inputs = None
         self.d_mps = None
+
+
+def headline_line(args, job, value, dt, world, strong, nctx, n_kp_img, verified, dist):
+    """The result line's headline part -- the same in a plain run and under --full (which adds its other figures to it)."""
+    stereo = job.matcher == "stereo"
+    B = job.B
+    # did the collective see N ranks?  the output of the LAST count all-gather of the timed region, cut into B-sized
+    # segments (one per rank, zero-initialised): a rank that did not take part leaves its segment at zero
+    coll = None
+    if world > 1:
+        segs = [int((g.view(world, B) != 0).any(dim=1).sum().item()) for g in job.gathered if g is not None]
+        coll = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "gathered_elements": int(job.gathered[0].numel()),
+                "elements_per_rank": B, "ranks_with_counts": min(segs) if args.gather_every else None,
+                "launcher": "bench.py spawn_ranks" if os.environ.get("GFO_BENCH_SPAWNED") else "external (torch.distributed.run)"}
+    return {
+        "metric": "frames/sec ORB extract+match, 752x480 @2000 kp" if args.workload == "stereo752" else f"frames/sec ORB {args.workload}",
+        "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        # ranks whose counts are in the last all-gather's output: `collective_ranks` whatever the backend, `rccl_ranks` only when
+        # the backend IS RCCL ("nccl"); a gloo rehearsal on one GPU reports rccl_ranks null
+        "collective_ranks": (coll["ranks_with_counts"] if coll else 1),
+        "rccl_ranks": ((coll["ranks_with_counts"] if coll["backend"] == "nccl" else None) if coll else 1), "collective": coll, "verified": verified,
+        "config": {"workload": job.cfg_name,
+                   "verified": ({k: verified[k] for k in ("images", "pairs", "mismatches")} if verified else None), "frame": "one camera image (a stereo pair = 2 frames + 1 association)",
+                   "images_per_step_per_gpu": B, "stereo_pairs_per_s": round(value / 2, 1) if stereo else None,
+                   "width": job.w, "height": job.h, "nfeatures": job.nfeat, "levels": 8, "scale_factor": 1.2, "fast_th": [20, 7],
+                   "map_points": MAP_POINTS if job.matcher == "project" else None,
+                   "mean_keypoints_per_image": round(n_kp_img, 1), "contexts_per_gpu": nctx,
+                   "contexts_chained_after_stage": job.chain_stage if job.chained else None,
+                   "priming_steps": PRIME_STEPS, "gather_every": args.gather_every if world > 1 else None,
+                   "distinct_input_batches": len(job.d_inputs),
+                   "sharding": ("single GPU" if world == 1 else
+                                f"ONE stream of {args.steps} batches, batch i -> rank i % {world} (shard_round_robin), all-gather of counts per round" if strong else
+                                f"{world} x independent streams, RCCL all-gather of counts")},
+    }
 
 
 def main():
@@ -933,6 +1035,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=HEADLINE_BATCH, help="images per GPU per step (even); 256 is where the rate levels off on MI355X (64 / 128 / 256 / 384 / 1024: 237k / 260k / 274k / 275k / 275k frames/s, profiles/batch_sweep_r03.txt)")
     ap.add_argument("--workload", default="stereo752", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else this benchmark measures and checks: the oracle check of the last step, "
+                         "the roofline (with its counter passes), sustained / strong-scaling / H2D / delivered / latency figures, the other "
+                         "BASELINE configs, real_image, per_frame_boundary, matcher_calls and the CPU baseline (the --no-* options below "
+                         "leave parts of it out).  Off by default: a plain run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed into DIR/<name>.npy (float32 / float64, "
+                         "under 64 MB in all: counts of every image, keypoints / descriptors / matcher outputs of a seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short passes over the other BASELINE configs")
     ap.add_argument("--profile-steps", type=int, default=10)
@@ -989,7 +1099,7 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world} in the environment: running {world} ranks (n_gpus reports {world})", file=sys.stderr)
     # the PMC passes run first, as children, while this process has not touched the GPU yet
     live, live_note = None, "live measurement off (--no-live-traffic)" if args.no_live_traffic else "N > 1: the counter passes are a single-GPU measurement"
-    if world == 1 and not args.no_live_traffic and not args.pmc_child and "GFO_BENCH_SPAWNED" not in os.environ:
+    if args.full and world == 1 and not args.no_live_traffic and not args.pmc_child and "GFO_BENCH_SPAWNED" not in os.environ:
         live, live_note = live_traffic(args.workload, args.batch - (args.batch & 1))
 
     import torch
@@ -1029,7 +1139,24 @@ def main():
         dt = job.timed(args.steps, args.warmup)
         total_frames = world * B * args.steps
     value = total_frames / dt
-    verified = job.verify() if rank == 0 and not args.no_verify else None
+    dumped = job.dump_outputs(args.dump_outputs) if rank == 0 and args.dump_outputs else None
+    verified = job.verify() if rank == 0 and args.full and not args.no_verify else None
+    if not args.full:
+        # a plain run: the headline and nothing else
+        line = None
+        if rank == 0:
+            counts = job.exts[job.last_ctx].batch_counts(B)
+            line = headline_line(args, job, value, dt, world, strong, nctx, float(counts.mean()), None, dist)
+            if dumped:
+                line["dumped_outputs"] = dumped
+        job.close()
+        del job
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # a timed region shorter than half a second says little about a sustained rate: repeat for >= 1 s
     sustained = None
@@ -1090,38 +1217,10 @@ def main():
     line = None
     if rank == 0:
         n_kp_img, roof = job.roofline(prof, args.profile_steps, value / world, args.workload, live, live_note)
-        stereo = job.matcher == "stereo"
-        # did the collective see N ranks?  the output of the LAST count all-gather of the timed region, cut into B-sized
-        # segments (one per rank, zero-initialised): a rank that did not take part leaves its segment at zero
-        coll = None
-        if world > 1:
-            segs = [int((g.view(world, B) != 0).any(dim=1).sum().item()) for g in job.gathered if g is not None]
-            coll = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "gathered_elements": int(job.gathered[0].numel()),
-                    "elements_per_rank": B, "ranks_with_counts": min(segs) if args.gather_every else None,
-                    "launcher": "bench.py spawn_ranks" if os.environ.get("GFO_BENCH_SPAWNED") else "external (torch.distributed.run)"}
-        line = {
-            "metric": "frames/sec ORB extract+match, 752x480 @2000 kp" if args.workload == "stereo752" else f"frames/sec ORB {args.workload}",
-            "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            # ranks whose counts are in the last all-gather's output: `collective_ranks` whatever the backend, `rccl_ranks` only when
-            # the backend IS RCCL ("nccl"); a gloo rehearsal on one GPU reports rccl_ranks null
-            "collective_ranks": (coll["ranks_with_counts"] if coll else 1),
-            "rccl_ranks": ((coll["ranks_with_counts"] if coll["backend"] == "nccl" else None) if coll else 1), "collective": coll, "verified": verified,
-            "config": {"workload": job.cfg_name,
-                       "verified": ({k: verified[k] for k in ("images", "pairs", "mismatches")} if verified else None), "frame": "one camera image (a stereo pair = 2 frames + 1 association)",
-                       "images_per_step_per_gpu": B, "stereo_pairs_per_s": round(value / 2, 1) if stereo else None,
-                       "width": job.w, "height": job.h, "nfeatures": job.nfeat, "levels": 8, "scale_factor": 1.2, "fast_th": [20, 7],
-                       "map_points": MAP_POINTS if job.matcher == "project" else None,
-                       "mean_keypoints_per_image": round(n_kp_img, 1), "contexts_per_gpu": nctx,
-                       "contexts_chained_after_stage": job.chain_stage if job.chained else None,
-                       "priming_steps": PRIME_STEPS, "gather_every": args.gather_every if world > 1 else None,
-                       "distinct_input_batches": len(job.d_inputs),
-                       "sharding": ("single GPU" if world == 1 else
-                                    f"ONE stream of {args.steps} batches, batch i -> rank i % {world} (shard_round_robin), all-gather of counts per round" if strong else
-                                    f"{world} x independent streams, RCCL all-gather of counts")},
-            "roofline": roof,
-        }
+        line = headline_line(args, job, value, dt, world, strong, nctx, n_kp_img, verified, dist)
+        line["roofline"] = roof
+        if dumped:
+            line["dumped_outputs"] = dumped
         if sustained:
             line["sustained"] = sustained
         if strong_beside:

@@ -1,11 +1,11 @@
-"""The C++ drop-in adapters EXECUTED on the GPU: tests/_build/adapter_run = adapter/ORBextractor_gfo.cc +
+"""The C++ drop-in adapters EXECUTED on the GPU: oracle/_ref/adapter_run = adapter/ORBextractor_gfo.cc +
 adapter/matchers_gfo.cc compiled against the reference's UNCHANGED headers (include/ORBextractor.h, Frame.h, MapPoint.h,
 ORBmatcher.h), linked with libgfo.so, driven the way Frame.cc / Tracking.cc drive the reference's classes
 (tests/host/adapter_run.cc lists the scenarios).  This file makes its inputs from the oracle's keypoints, runs the program once
 and compares everything it wrote with the oracle, bit for bit.
 
-The binary is built by __graft_entry__.build() where the reference headers are mounted (the build container) and travels to the
-GPU box with the snapshot, like libgfo.so."""
+The binary is built by __graft_entry__.build() where the reference headers are (oracle/Makefile `adapter`) and goes with the rest
+of oracle/_ref/ to the machine that runs the GPU tests."""
 import os
 import subprocess
 
@@ -16,7 +16,7 @@ from conftest import ROOT, GOLDEN
 
 pytestmark = pytest.mark.gpu
 
-EXE = os.path.join(ROOT, "tests", "_build", "adapter_run")
+EXE = os.path.join(ROOT, "oracle", "_ref", "adapter_run")
 FX, FY, CX, CY = 435.2046959714599, 435.2046959714599, 367.4517211914062, 252.2008514404297
 MBF = np.float32(47.906)
 MB = np.float32(np.float32(47.906) / np.float32(435.2))
@@ -57,12 +57,12 @@ def _pose(rx, ry, rz, t):
 def run(tmp_path_factory, oracle, euroc_l, euroc_r):
     if not os.path.exists(EXE):
         if os.path.exists("/root/reference/include/ORBextractor.h"):
-            subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "host")])
+            subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "adapter"])
         else:
             # (a skip, not a failure: the suite runs with -x and everything behind this file would go unreported; the skip reason is
             #  in the report, and GPUTEST's pass count shows these eleven tests missing)
-            pytest.skip("tests/_build/adapter_run is missing and the reference headers are not mounted here: "
-                        "__graft_entry__.build() makes the binary in the build container and it travels with the snapshot")
+            pytest.skip("oracle/_ref/adapter_run is missing and the reference headers are not here: "
+                        "__graft_entry__.build() makes the binary where they are and it goes with oracle/_ref/")
     ind, outd = tmp_path_factory.mktemp("adapter_in"), tmp_path_factory.mktemp("adapter_out")
     oe = oracle.OracleExtractor(2000, 1.2, 8, 20, 7)
     sf = oe.scale_factors
@@ -106,7 +106,7 @@ def run(tmp_path_factory, oracle, euroc_l, euroc_r):
     SF4.prepare()
     ref["D4"] = SF4.match(min_d, max_d, has.astype(np.uint8))
     ref["D_windows_used"] = int(ok.sum())
-    # DD: the same frame as a DELAYED_STEREO_MATCHING build drives it (tests/_build/adapter_run_delayed): map points arrive in two
+    # DD: the same frame as a DELAYED_STEREO_MATCHING build drives it (oracle/_ref/adapter_run_delayed): map points arrive in two
     # stages, an online call after each, then two offline calls (Frame.cc:1186-1199)
     stage = np.where(has, np.where(rng.random(n) < 0.6, 1, 2), 0).astype(np.int32)
     stage.tofile(ind / "DD_stage.bin")
@@ -225,7 +225,7 @@ def run(tmp_path_factory, oracle, euroc_l, euroc_r):
                                                            100, bool(ori), np.zeros(len(kl1), np.uint8))
         ref["F"].append({"nm": nm, "idx": np.where(out_q >= 0, qi[np.maximum(out_q, 0)], -1).astype(np.int32), "visible": len(qi),
                          "fwd": fwd, "bwd": bwd})
-        with oracle.feature_budget(BUDGET):        # the same call in a BUDGETING_FEATURE_MATCHING build (tests/_build/adapter_run_budget)
+        with oracle.feature_budget(BUDGET):        # the same call in a BUDGETING_FEATURE_MATCHING build (oracle/_ref/adapter_run_budget)
             nmb, out_qb, _ = oracle.search_by_projection_queries(kl1, dl1, st1[1], kl1["angle"], (0.0, 0.0, 752.0, 480.0), q, qd[qi], False, 0.0,
                                                                  100, bool(ori), np.zeros(len(kl1), np.uint8))
         ref.setdefault("F_budget", []).append({"nm": nmb, "idx": np.where(out_qb >= 0, qi[np.maximum(out_qb, 0)], -1).astype(np.int32)})
@@ -799,7 +799,7 @@ def test_stereo_member_of_a_delayed_stereo_matching_build(run):
     unvisited keypoints that carry a map point, the offline call the other unvisited ones (Frame.cc:1186-1199), state and
     mvDistIdx run through all four calls of the frame; against the oracle's literal member (orc_stereo_frame, delayed = 1)"""
     if "delayed" not in run:
-        pytest.skip("tests/_build/adapter_run_delayed is missing (built by __graft_entry__.build() where the reference headers are)")
+        pytest.skip("oracle/_ref/adapter_run_delayed is missing (built by __graft_entry__.build() where the reference headers are)")
     d = run["delayed"]
     assert d["rc"] == 0, d["stderr"][-3000:]
     assert "[gfo]" not in d["stderr"], d["stderr"][-2000:]
@@ -1005,7 +1005,7 @@ def test_matcher_members_of_a_budgeting_feature_matching_build(run):
     (ORBmatcher.cc:1547-1552); SearchByBoW leaves a node's loop once 150 is reached, every later node still adds its first match
     (:360-365).  Against the oracle compiled the same way (orc_set_feature_budget); everything else of the program is unchanged."""
     if "budget" not in run:
-        pytest.skip("tests/_build/adapter_run_budget is missing (built by __graft_entry__.build() where the reference headers are)")
+        pytest.skip("oracle/_ref/adapter_run_budget is missing (built by __graft_entry__.build() where the reference headers are)")
     b = run["budget"]
     assert b["rc"] == 0, b["stderr"][-3000:]
     assert "[gfo]" not in b["stderr"], b["stderr"][-2000:]

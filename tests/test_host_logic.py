@@ -208,6 +208,20 @@ def test_bench_gpus_n_is_its_own_launcher_and_stays_off_the_gpu():
     assert r.returncode == 0 and r.stdout.strip() == "" and '"rank": 1' in r.stderr
 
 
+def test_bench_full_and_dump_outputs_are_options_and_off_by_default():
+    """bench.py's --full (everything beside the headline) and --dump-outputs DIR are options, both off by default."""
+    import importlib.util
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert callable(bench.Job.dump_outputs) and callable(bench.headline_line)
+
+
 def test_combiner_under_thread_sanitizer(tmp_path):
     """gf-orb-slam2_amd/csrc/gfo_combine.hip -- engine slots, forming batches, the GfoPair rendezvous with its
     lock-free state mirror, dormancy / wake counts -- compiled UNMODIFIED for the CPU with -fsanitize=thread against a fake backend

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out
 i=0
 for SPEC in "$@"; do
   i=$((i+1))
-  ENVS="${SPEC%%--*}"; ARGS="${SPEC#*--}"
+  ENVS="${SPEC%%--*}"; ARGS="--full ${SPEC#*--}"     # (the stage times and `sustained` read below are --full figures)
   for rep in 1 2; do
     env $ENVS python bench.py --steps ${GFO_AB_STEPS:-100} --warmup 30 --no-cpu-baseline --no-other-configs --no-boundary --no-live-traffic $ARGS > gpurun_out/aa_$i.json 2> gpurun_out/aa_$i.err || { tail -5 gpurun_out/aa_$i.err; exit 1; }
     python - "$SPEC" gpurun_out/aa_$i.json <<'PY'

@@ -2,6 +2,7 @@
 # k_blur with all blocks of an image on one XCD (GFO_BLUR_XCD=1) against the plain (blocks, images) grid: FETCH_SIZE / WRITE_SIZE per launch and stage times, one box.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out; OUTF=$R/gpurun_out/ab_blur_xcd.txt; : > $OUTF
+T=$(mktemp -d)     # this A/B's bench lines, each read once below (stage times and `sustained` are bench.py --full figures)
 for X in 0 1; do
   export GFO_BLUR_XCD=$X
   for CTR in FETCH_SIZE WRITE_SIZE; do
@@ -17,10 +18,10 @@ print(f"GFO_BLUR_XCD={sys.argv[3]} {sys.argv[2]} MB per launch: " + "  ".join(f"
 PY
   done
   for rep in 1 2; do
-    python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-other-configs --no-boundary --no-live-traffic --no-verify > gpurun_out/abbx.json 2> gpurun_out/abbx.err || { tail -5 gpurun_out/abbx.err; exit 1; }
-    python3 - $X <<'PY' | tee -a $OUTF
+    python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-other-configs --no-boundary --no-live-traffic --no-verify --full > $T/abbx.json 2> $T/abbx.err || { tail -5 $T/abbx.err; exit 1; }
+    python3 - $X $T/abbx.json <<'PY' | tee -a $OUTF
 import json, sys
-j = json.loads(open('gpurun_out/abbx.json').read().strip().splitlines()[-1])
+j = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 st = j["roofline"]["stage_ms_per_step"]
 print(f"GFO_BLUR_XCD={sys.argv[1]} value {j['value']:.0f}  " + " ".join(f"{k}={v*1e3:.1f}" for k, v in st.items() if k.startswith(('blur','quadtree'))))
 PY

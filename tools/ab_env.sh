@@ -1,6 +1,7 @@
 #!/bin/bash
 # Same-box A/B of environment settings: tools/ab_env.sh "VAR=val VAR2=val" "" ...   ("" = defaults); two short bench runs each
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out
+GFO_AB_ARGS="--full ${GFO_AB_ARGS}"     # the stage times read below are part of bench.py --full
 for rep in 1 2; do
 for E in "$@"; do
   env $E python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-other-configs --no-boundary --no-live-traffic ${GFO_AB_ARGS} > gpurun_out/abe.json 2> gpurun_out/abe.err || { tail -5 gpurun_out/abe.err; exit 1; }

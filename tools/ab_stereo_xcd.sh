@@ -4,6 +4,7 @@
 # usage (through gpurun): tools/ab_stereo_xcd.sh   -> gpurun_out/ab_stereo_xcd.txt
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out; OUTF=$R/gpurun_out/ab_stereo_xcd.txt; : > $OUTF
+T=$(mktemp -d)     # this A/B's bench lines, each read once below (stage times and `sustained` are bench.py --full figures)
 for X in 0 1; do
   export GFO_STEREO_XCD=$X
   for CTR in FETCH_SIZE WRITE_SIZE; do
@@ -19,10 +20,10 @@ print(f"GFO_STEREO_XCD={sys.argv[3]} {sys.argv[2]} MB per launch: " + "  ".join(
 PY
   done
   for rep in 1 2; do
-    python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-other-configs --no-boundary --no-live-traffic --no-verify > gpurun_out/absx.json 2> gpurun_out/absx.err || { tail -5 gpurun_out/absx.err; exit 1; }
-    python3 - $X <<'PY' | tee -a $OUTF
+    python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-other-configs --no-boundary --no-live-traffic --no-verify --full > $T/absx.json 2> $T/absx.err || { tail -5 $T/absx.err; exit 1; }
+    python3 - $X $T/absx.json <<'PY' | tee -a $OUTF
 import json, sys
-j = json.loads(open('gpurun_out/absx.json').read().strip().splitlines()[-1])
+j = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 st = j["roofline"]["stage_ms_per_step"]
 print(f"GFO_STEREO_XCD={sys.argv[1]} value {j['value']:.0f}  " + " ".join(f"{k}={v*1e3:.1f}" for k, v in st.items() if k.startswith('stereo')))
 PY

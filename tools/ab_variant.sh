@@ -3,6 +3,7 @@
 # with each (GFO_LIB selects the library), printing value and the per-stage times.
 # usage (through gpurun): tools/ab_variant.sh "<flags A>" "<flags B>" ...     ("" = the library as built)
 R=$GRAFT_REPO_ROOT; cd $R; mkdir -p gpurun_out
+GFO_AB_ARGS="--full ${GFO_AB_ARGS}"     # the stage times read below are part of bench.py --full
 i=0
 for FL in "$@"; do
   i=$((i+1))

@@ -11,5 +11,6 @@ tools/boundary_throughput.sh ${TAG}_pinned 3 stereo 1,2,4,8,16 1 1 > /dev/null |
 tools/boundary_throughput.sh ${TAG}_nocombine 3 both 1,2,4,8,16 0 0 > /dev/null || exit 5
 tools/latency_pair.sh $TAG > /dev/null || exit 6
 tools/trace_boundary.sh ${TAG}_k8_combined 8 stereo 0 1 > /dev/null || exit 8
-python bench.py > gpurun_out/bench_default_$TAG.json 2> gpurun_out/bench_default_$TAG.err || exit 9
+# the full bench line (every figure besides the headline: bench.py --full) is a record as it stands: straight into profiles/
+python bench.py --full > profiles/bench_default_$TAG.json || exit 9
 echo "round profiles $TAG done"

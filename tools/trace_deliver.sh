@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 TAG=$1; export GFO_DELIVER_DMA=${2:-0}
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/trace_deliver_$TAG; rm -rf $OUT; mkdir -p $OUT; cd $R
-timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -- python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --no-boundary --profile-steps 1 > $OUT/log.txt 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -- python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs --no-boundary --profile-steps 1 > $OUT/log.txt 2>&1
 python3 - "$OUT" <<'PY' | tee $R/gpurun_out/trace_deliver_$TAG.txt
 import csv, glob, os, sys, collections
 root = sys.argv[1]
