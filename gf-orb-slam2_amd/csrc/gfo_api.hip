@@ -344,6 +344,29 @@ int gfo_plan(gfo_ctx* c, int w, int h, int batch)
         }
 #endif
     }
+    // the strips of GFO_RESIZE_ROWS rows the batch-path kernels run on their rolling-row path (k_pyramid.hip rs_strip):
+    // leading strips whose rows blend (sy, sy + 1) with sy growing and 0 <= sy, sy + 1 < sh - 1, on a level where every
+    // column quad's taps lie within 8 bytes of its first one
+    for (int l = 1; l < g.nlevels; l++) {
+        GfoLevel& L = g.lv[l];
+        const int sh = g.lv[l - 1].h, R = GFO_RESIZE_ROWS;
+        L.rs_fast_strips = 0;
+        bool cols_ok = true;
+        for (int q = 0; 4 * q < L.w && cols_ok; q++) {
+            const int* e = &xtabv[2 * (size_t)(L.xtab_off + 4 * q)];   // the level's table is padded by 3 entries
+            cols_ok = e[6] + 1 - e[0] < 8;
+        }
+        if (!cols_ok) continue;
+        for (int s_ = 0; s_ * R < L.h; s_++) {
+            bool ok = true;
+            for (int d = s_ * R; d < std::min(s_ * R + R, L.h) && ok; d++) {
+                const int sy = ytabv[2 * (size_t)(L.ytab_off + d)];
+                ok = sy >= 0 && sy + 1 < sh - 1 && (d == s_ * R || sy > ytabv[2 * (size_t)(L.ytab_off + d - 1)]);
+            }
+            if (!ok) break;
+            L.rs_fast_strips = s_ + 1;
+        }
+    }
     // banded pyramid: the levels are cut into groups of consecutive levels, each one launch of k_pyramid_bands
     // (a group of ONE level is an ordinary k_resize launch).  Greedy from level 1: the longest group (up to
     // GFO_PYR_GROUP levels) for which some band count <= 64 keeps the per-workgroup LDS footprint within the

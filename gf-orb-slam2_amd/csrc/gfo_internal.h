@@ -17,6 +17,11 @@
 #include "../../include/gfo.h"
 
 // [OCV] build variants (include/gfo.h gfo_build_variant; same values as the checker's ocv_variants.json).  `make EXTRA="-DGFO_OCV_RESIZE=1"`.
+// output rows per wave of the batch-path k_resize / k_resize_tail (k_pyramid.hip)
+#ifndef GFO_RESIZE_ROWS
+#define GFO_RESIZE_ROWS 8
+#endif
+
 #ifndef GFO_OCV_RESIZE
 #define GFO_OCV_RESIZE 0        // 0: 11-bit fixed-point bilinear (resizeGeneric_), 1: float bilinear, rounded half to even once
 #endif
@@ -72,6 +77,9 @@ struct GfoLevel {
     int patch_size;           // int(31*scale)
     // resize tables: offsets (in elements) into the table buffers
     int xtab_off, ytab_off;
+    // batch-path k_resize / k_resize_tail: strips [0, rs_fast_strips) of GFO_RESIZE_ROWS rows take the rolling-row path
+    // (k_pyramid.hip rs_strip), the rest resize_block
+    int rs_fast_strips;
 };
 
 // One launch of the banded pyramid: levels [lb, le) in nb bands per image

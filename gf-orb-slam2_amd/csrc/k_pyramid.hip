@@ -2,7 +2,9 @@
 // INTER_LINEAR) in OpenCV's 11-bit fixed point.  The coefficient tables (xofs/alpha, yofs/beta)
 // are built on the host in double exactly as cv::resize builds them (gfo_api.hip, plan()).
 //
-// HBM-bound byte work.  A thread owns a 4x4 block of output pixels: the column tables are read once,
+// The batch path's per-level kernels (k_resize, k_resize_tail) walk strips of GFO_RESIZE_ROWS rows (rs_strip, below); the
+// banded form and the irregular rows of those kernels use resize_block:
+// a thread owns a 4x4 block of output pixels: the column tables are read once,
 // the <= 6 source rows the block touches are fetched up front as three coalesced dwords each (12 bytes
 // cover the <= 11-byte footprint of 4 outputs for scale factors up to 2) so every load of the thread is
 // in flight at once, each source row is filtered horizontally once, and the four output rows are
@@ -226,6 +228,29 @@ __device__ __forceinline__ void zero_candidate_counters(int* __restrict__ zero_c
     if (zero_cnt && tid < nlevels) zero_cnt[(img * nlevels + tid) * GFO_CNT_STRIDE] = 0;
 }
 
+// register budget of the per-level kernel (the 1080p path: its levels do not fit the banded form): 8 waves per SIMD =
+// 64 registers instead of 73; 55.9k -> 58.8k frames/s for extract-only 1080p (same-box A/B), 7 gives half of that
+#ifndef GFO_RESIZE_WAVES
+#define GFO_RESIZE_WAVES 8
+#endif
+#if GFO_RESIZE_WAVES > 0
+#define RESIZE_OCC_ATTR __attribute__((amdgpu_waves_per_eu(GFO_RESIZE_WAVES, GFO_RESIZE_WAVES)))
+#else
+#define RESIZE_OCC_ATTR
+#endif
+// The small top levels of the pyramid are launch-latency bound as separate kernels (each is a dependent
+// launch that cannot fill the chip).  One 1024-thread workgroup per image computes levels
+// [level_begin, nlevels) back to back: a workgroup barrier orders level l's stores before level l+1's loads
+// (same CU, same L1/L2 path).
+#ifndef GFO_TAIL_WAVES
+#define GFO_TAIL_WAVES 0
+#endif
+#if GFO_TAIL_WAVES > 0
+#define TAIL_OCC_ATTR __attribute__((amdgpu_waves_per_eu(GFO_TAIL_WAVES, GFO_TAIL_WAVES)))
+#else
+#define TAIL_OCC_ATTR
+#endif
+#ifdef GFO_RESIZE_V1
 // Whole-plane form: level `level` of image `img` from the plane below it in HBM.
 template <bool UNI>
 __device__ __forceinline__ void resize_plane_block(const GfoGeom& g, const GfoInput& in, uint8_t* __restrict__ pyr, int level,
@@ -241,16 +266,6 @@ __device__ __forceinline__ void resize_plane_block(const GfoGeom& g, const GfoIn
                              xtab_all + L.xtab_off, ytab_all + L.ytab_off, level - 1 == 0 ? 2 : 1);
 }
 
-// register budget of the per-level kernel (the 1080p path: its levels do not fit the banded form): 8 waves per SIMD =
-// 64 registers instead of 73; 55.9k -> 58.8k frames/s for extract-only 1080p (same-box A/B), 7 gives half of that
-#ifndef GFO_RESIZE_WAVES
-#define GFO_RESIZE_WAVES 8
-#endif
-#if GFO_RESIZE_WAVES > 0
-#define RESIZE_OCC_ATTR __attribute__((amdgpu_waves_per_eu(GFO_RESIZE_WAVES, GFO_RESIZE_WAVES)))
-#else
-#define RESIZE_OCC_ATTR
-#endif
 __global__ __launch_bounds__(256) RESIZE_OCC_ATTR void k_resize(const GfoGeom* __restrict__ gp, GfoInput in, uint8_t* __restrict__ pyr,
                                                 int level, const int2* __restrict__ xtab_all,
                                                 const int2* __restrict__ ytab_all, int* __restrict__ zero_cnt)
@@ -269,18 +284,6 @@ __global__ __launch_bounds__(256) RESIZE_OCC_ATTR void k_resize(const GfoGeom* _
     resize_plane_block<true>(g, in, pyr, level, blockIdx.y, quad, strip, xtab_all, ytab_all);
 }
 
-// The small top levels of the pyramid are launch-latency bound as separate kernels (each is a dependent
-// launch that cannot fill the chip).  One 1024-thread workgroup per image computes levels
-// [level_begin, nlevels) back to back: a workgroup barrier orders level l's stores before level l+1's loads
-// (same CU, same L1/L2 path).
-#ifndef GFO_TAIL_WAVES
-#define GFO_TAIL_WAVES 0
-#endif
-#if GFO_TAIL_WAVES > 0
-#define TAIL_OCC_ATTR __attribute__((amdgpu_waves_per_eu(GFO_TAIL_WAVES, GFO_TAIL_WAVES)))
-#else
-#define TAIL_OCC_ATTR
-#endif
 __global__ __launch_bounds__(1024) TAIL_OCC_ATTR void k_resize_tail(const GfoGeom* __restrict__ gp, GfoInput in, uint8_t* __restrict__ pyr,
                                                       int level_begin, const int2* __restrict__ xtab_all,
                                                       const int2* __restrict__ ytab_all, int* __restrict__ zero_cnt)
@@ -301,6 +304,200 @@ __global__ __launch_bounds__(1024) TAIL_OCC_ATTR void k_resize_tail(const GfoGeo
         __syncthreads();
     }
 }
+
+#else
+// The batch path, per-level kernels (k_resize: the big levels, one launch each; k_resize_tail: the small top levels).
+// A wave owns one strip of RS_ROWS output rows of ONE level and up to 64 column quads of it, a lane one quad, so
+// every row index and row coefficient is the same for all lanes: the row table is read by scalar loads, the source
+// and output rows are scalar bases with a 32-bit lane offset, and which source rows an output row blends is decided
+// by scalar branches.  Walking the strip top to bottom, a lane keeps the horizontal sums of the last two source
+// rows it filtered and filters a source row only when an output row first needs it (at scale 1.2: 1.2 source rows
+// per output row instead of 1.5 for the 4-row blocks of resize_block).  Source rows are loaded one output row ahead.
+// (-DGFO_RESIZE_V1 builds the 4x4-block kernels instead, for same-source A/Bs.)
+#define RS_ROWS GFO_RESIZE_ROWS   // gfo_internal.h
+
+// A lane's column quad: fixed over the strip.
+struct RsCols {
+    unsigned off;     // base_x = sx[0] & ~3: the first byte of the 12-byte row window
+    unsigned o0;      // sx[0] - base_x
+    unsigned sel[4];  // v_perm selectors {byte rel_k, 0, byte rel_k + 1, 0}
+    int cw[4];        // packed column coefficients
+};
+
+typedef unsigned gfo_u32x3 __attribute__((ext_vector_type(3)));
+
+// Plane addressing: a buffer resource on the plane (scalar), the row's byte offset in the scalar offset and the lane's
+// 32-bit offset in the row: no 64-bit address per lane.  (Raw buffer, no range check in effect: num_records is 2^32 - 1.)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rs_rsrc(const void* base)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, -1, 0x00020000);
+}
+
+// One source row's 12-byte window -> a lane's four horizontal sums, as the vertical blend takes them: OCV 0: h >> 4
+// (VResizeLinear shifts each row's sum once; done here, once per source row, instead of once per output row that uses
+// it); OCV 1: the float bits.
+__device__ __forceinline__ void rs_hsum(const RsCols& c, gfo_u32x3 w, unsigned (&h)[4])
+{
+    const unsigned A = __builtin_amdgcn_alignbyte(w.y, w.x, c.o0), B = __builtin_amdgcn_alignbyte(w.z, w.y, c.o0);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const unsigned two = __builtin_amdgcn_perm(B, A, c.sel[k]);
+#if GFO_OCV_RESIZE == 1
+        h[k] = (unsigned)resize_hlerp(two & 0xFFFFu, two >> 16, c.cw[k]);
+#else
+        h[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(gfo_u16x2, two), __builtin_bit_cast(gfo_u16x2, (unsigned)c.cw[k]), 0u, false) >> 4;
+#endif
+    }
+}
+
+// Four output bytes of one row from the two source rows' sums and the row's table entry bw = b0 | b1 << 16.
+//   OCV 0: ((b0 * x0) >> 16) == mul_hi(b0 << 16, x0) exactly for b0 < 2^16 (both shift in SGPRs), so each byte is two
+//   v_mul_hi_u32 and one v_add3_u32; the >> 2 runs on two bytes at once (v_pk_lshrrev_b16) and one v_perm_b32 packs.
+//   (tests/test_resize_blend.py checks the identity against resize_vblend over the whole range of b and h.)
+__device__ __forceinline__ unsigned rs_blend(unsigned bw, const unsigned (&ht)[4], const unsigned (&hb)[4])
+{
+#if GFO_OCV_RESIZE == 1
+    unsigned packed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) packed |= resize_vblend((int)bw, (int)ht[k], (int)hb[k]) << (8 * k);
+    return packed;
+#else
+    const unsigned b0s = bw << 16, b1s = bw & 0xFFFF0000u;
+    unsigned s[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) s[k] = __umulhi(b0s, ht[k]) + __umulhi(b1s, hb[k]) + 2u;   // <= 1022
+    const gfo_u16x2 s01 = __builtin_bit_cast(gfo_u16x2, s[0] | (s[1] << 16)) >> (unsigned short)2;
+    const gfo_u16x2 s23 = __builtin_bit_cast(gfo_u16x2, s[2] | (s[3] << 16)) >> (unsigned short)2;
+    return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, s23), __builtin_bit_cast(unsigned, s01), 0x06040200u);
+#endif
+}
+
+// One strip of a level: output rows [dy0, min(dy0 + RS_ROWS, dh)), column quad `quad` (< the level's quads).
+// src / dst are the planes (sw x sh, dw x dh); every argument but `quad` is wave-uniform.  Only for the strips plan()
+// counted into GfoLevel.rs_fast_strips: every output row blends rows (sy, sy + 1) with 0 <= sy, sy + 1 < sh - 1 (no
+// clamped row, and no row the window may not overrun: see resize_block), sy grows down the strip, and every quad's
+// window covers its taps.
+__device__ __forceinline__ void rs_strip(const uint8_t* __restrict__ src, int spitch, uint8_t* __restrict__ dst, int dpitch,
+                                         int dh, int quad, int dy0, const int2* __restrict__ xtab, const int2* __restrict__ ytab)
+{
+    const unsigned dx0 = (unsigned)quad * 4u;
+    const int4* xt = reinterpret_cast<const int4*>(xtab + dx0);
+    const int4 xa = xt[0], xb = xt[1];
+    RsCols c;
+    const int sx[4] = {xa.x, xa.z, xb.x, xb.z};
+    c.cw[0] = xa.y; c.cw[1] = xa.w; c.cw[2] = xb.y; c.cw[3] = xb.w;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const unsigned rel = (unsigned)(sx[k] - sx[0]) & 7u;
+        c.sel[k] = rel | (0x0Cu << 8) | ((rel + 1u) << 16) | (0x0Cu << 24);
+    }
+    c.off = (unsigned)(sx[0] & ~3);
+    c.o0 = (unsigned)sx[0] & 3u;
+    const __amdgpu_buffer_rsrc_t sr = rs_rsrc(src), dr = rs_rsrc(dst);
+    const int n = min(RS_ROWS, dh - dy0);
+    // the rows (scalar): output row j blends source rows sy[j], sy[j] + 1; its top row is the previous bottom row or new
+    int sy[RS_ROWS];
+    unsigned bw[RS_ROWS];
+#pragma unroll
+    for (int j = 0; j < RS_ROWS; j++) {
+        const int2 e = ytab[dy0 + min(j, n - 1)];   // rows past the level repeat its last row (never used)
+        sy[j] = e.x;
+        bw[j] = (unsigned)e.y;
+    }
+    gfo_u32x3 wt[RS_ROWS], wb[RS_ROWS];
+    wt[0] = __builtin_amdgcn_raw_buffer_load_b96(sr, c.off, sy[0] * spitch, 0);
+    wb[0] = __builtin_amdgcn_raw_buffer_load_b96(sr, c.off, (sy[0] + 1) * spitch, 0);
+    unsigned hb[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < RS_ROWS; j++) {
+        if (j >= n) break;
+        if (j + 1 < RS_ROWS && j + 1 < n) {   // the next row's loads go out before this row's arithmetic
+            if (sy[j + 1] != sy[j] + 1) wt[j + 1] = __builtin_amdgcn_raw_buffer_load_b96(sr, c.off, sy[j + 1] * spitch, 0);
+            wb[j + 1] = __builtin_amdgcn_raw_buffer_load_b96(sr, c.off, (sy[j + 1] + 1) * spitch, 0);
+        }
+        unsigned nt[4], nb[4];
+        if (j == 0 || sy[j] != sy[j - 1] + 1) {
+            rs_hsum(c, wt[j], nt);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) nt[k] = hb[k];
+        }
+        rs_hsum(c, wb[j], nb);
+        // pitches are multiples of 16: the dword stays in-row
+        __builtin_amdgcn_raw_buffer_store_b32(rs_blend(bw[j], nt, nb), dr, dx0, (dy0 + j) * dpitch, 0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) hb[k] = nb[k];
+    }
+}
+
+// The tasks of a level: its first rs_fast_strips strips of RS_ROWS rows, then the rest of its rows in 4-row blocks
+// (resize_block: the clamped last rows, the caller's image's last rows, steep scale factors).  A wave takes one task of
+// up to 64 quads.
+__device__ __forceinline__ int rs_tasks(const GfoLevel& L)
+{
+    return L.rs_fast_strips + max(L.h - L.rs_fast_strips * RS_ROWS + RS_STRIP - 1, 0) / RS_STRIP;   // the last strip may be short
+}
+
+// task `task` of level `level` of image `img`, column quad `quad`, from the plane below it in HBM
+__device__ __forceinline__ void rs_plane_task(const GfoGeom& g, const GfoInput& in, uint8_t* __restrict__ pyr, int level, int img,
+                                              int quad, int task, const int2* __restrict__ xtab_all,
+                                              const int2* __restrict__ ytab_all)
+{
+    const GfoLevel& L = g.lv[level];
+    int spitch;
+    const uint8_t* src = gfo_level_ptr(g, in, pyr, level - 1, img, &spitch);
+    uint8_t* dst = pyr + (long long)img * g.pyr_img_stride + L.plane_off;
+    const int2* xtab = xtab_all + L.xtab_off;
+    const int2* ytab = ytab_all + L.ytab_off;
+    if (task < L.rs_fast_strips) {
+        rs_strip(src, spitch, dst, L.pitch, L.h, quad, task * RS_ROWS, xtab, ytab);
+        return;
+    }
+    const int sh = g.lv[level - 1].h, sw = g.lv[level - 1].w;
+    resize_block<true, false>(src, spitch, 0, sh - 1, sh, sw, dst, L.pitch, 0, L.h, nullptr, 0, 0, L.h, quad,
+                              L.rs_fast_strips * RS_ROWS + (task - L.rs_fast_strips) * RS_STRIP, xtab, ytab, level - 1 == 0 ? 2 : 1);
+}
+
+__global__ __launch_bounds__(256) RESIZE_OCC_ATTR void k_resize(const GfoGeom* __restrict__ gp, GfoInput in, uint8_t* __restrict__ pyr,
+                                                int level, const int2* __restrict__ xtab_all,
+                                                const int2* __restrict__ ytab_all, int* __restrict__ zero_cnt)
+{
+    const GfoGeom& g = *gp;
+    if (blockIdx.x == 0) zero_candidate_counters(zero_cnt, blockIdx.y, g.nlevels, threadIdx.x);
+    const GfoLevel& L = g.lv[level];
+    const int quads = (L.w + 3) >> 2;
+    const int wps = (quads + 63) >> 6;
+    const int wv = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6);
+    const int task = wv / wps;
+    const int quad = (wv - task * wps) * 64 + (threadIdx.x & 63);
+    if (task >= rs_tasks(L) || quad >= quads) return;
+    rs_plane_task(g, in, pyr, level, blockIdx.y, quad, task, xtab_all, ytab_all);
+}
+
+// one workgroup per image: the waves take the (task, 64-quad chunk) pieces of a level, so a wave never spans two strips
+__global__ __launch_bounds__(1024) TAIL_OCC_ATTR void k_resize_tail(const GfoGeom* __restrict__ gp, GfoInput in, uint8_t* __restrict__ pyr,
+                                                      int level_begin, const int2* __restrict__ xtab_all,
+                                                      const int2* __restrict__ ytab_all, int* __restrict__ zero_cnt)
+{
+    const GfoGeom& g = *gp;
+    const int img = blockIdx.x;
+    zero_candidate_counters(zero_cnt, img, g.nlevels, threadIdx.x);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int nwaves = blockDim.x >> 6;
+    for (int level = level_begin; level < g.nlevels; level++) {
+        const GfoLevel& L = g.lv[level];
+        const int quads = (L.w + 3) >> 2;
+        const int wps = (quads + 63) >> 6;
+        for (int t = wave; t < wps * rs_tasks(L); t += nwaves) {
+            const int task = t / wps;
+            const int quad = (t - task * wps) * 64 + lane;
+            if (quad < quads) rs_plane_task(g, in, pyr, level, img, quad, task, xtab_all, ytab_all);
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+#endif
 
 // Banded form (large batches): a workgroup owns a horizontal band of the image through a GROUP of consecutive
 // levels [lb, le).  It computes the band of level lb from the plane below it in HBM, keeps it in LDS, computes
@@ -366,8 +563,13 @@ __global__ __launch_bounds__(1024) BANDS_OCC_ATTR void k_pyramid_bands(const Gfo
 void gfo_launch_resize(gfo_ctx* c, const GfoInput& in, int level, int nimg)
 {
     const GfoLevel& L = c->g.lv[level];
-    const int quads = (L.w + 3) / 4, strips = (L.h + RS_STRIP - 1) / RS_STRIP;
-    const int waves = ((quads + 63) / 64) * strips;
+    const int quads = (L.w + 3) / 4;
+#ifdef GFO_RESIZE_V1
+    const int tasks = (L.h + RS_STRIP - 1) / RS_STRIP;
+#else
+    const int tasks = L.rs_fast_strips + std::max(L.h - L.rs_fast_strips * RS_ROWS + RS_STRIP - 1, 0) / RS_STRIP;   // rs_tasks
+#endif
+    const int waves = ((quads + 63) / 64) * tasks;
     dim3 grid((waves + 3) / 4, nimg);
     gfo_prof_begin(c, ST_RESIZE);
     GFO_LAUNCH(c, k_resize, grid, dim3(256), 0, c->stream, c->d_geom, in, c->d_pyr, level,
