@@ -8,10 +8,11 @@ from ._lib import GfoError, KEYPOINT_DTYPE, MAP_POINT_DTYPE, PROJ_QUERY_DTYPE, l
 from .extractor import ORBextractor  # noqa: F401
 from .matcher import ORBmatcher, ORBVocabulary, StereoParams, FrameBounds  # noqa: F401
 from .build import build_library, build_variants  # noqa: F401
+from .undistort import image_bounds  # noqa: F401
 
 # images per GPU per step of bench.py's headline workload AND of the parity test at that shape (tests/test_gpu_properties.py):
 # one constant, so that what is timed is what is compared with the oracle
 HEADLINE_BATCH = 256
 
 __all__ = ["HEADLINE_BATCH", "ORBextractor", "ORBmatcher", "ORBVocabulary", "StereoParams", "FrameBounds", "GfoError", "KEYPOINT_DTYPE",
-           "MAP_POINT_DTYPE", "build_library", "build_variants", "load_library", "lib_path"]
+           "MAP_POINT_DTYPE", "build_library", "build_variants", "image_bounds", "load_library", "lib_path"]

@@ -63,6 +63,11 @@ class DeliveryC(C.Structure):
                                           "off_best_idx", "off_nmatched", "bytes")]
 
 
+class CameraC(C.Structure):
+    _fields_ = [("K", C.c_float * 9), ("D", C.c_float * 8), ("n_dist", C.c_int32), ("R", C.c_float * 9), ("P", C.c_float * 12),
+                ("has_R", C.c_int32), ("has_P", C.c_int32)]
+
+
 class StageTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("ms", C.c_double), ("launches", C.c_int)]
 
@@ -78,6 +83,7 @@ SYMBOLS = [
     "gfo_profile_read", "gfo_debug_blurred_level", "gfo_debug_level_candidates",
     "gfo_contexts_created", "gfo_arenas_planned", "gfo_kernels_preloaded", "gfo_ctx_id", "gfo_vocabulary_nodes", "gfo_ctx_set_combining", "gfo_combiner_stats", "gfo_ctx_pair", "gfo_combiner_counters", "gfo_tuning_set", "gfo_tuning_get",
     "gfo_batch_deliver", "gfo_deliver_wait", "gfo_host_register", "gfo_host_unregister",
+    "gfo_ctx_set_camera", "gfo_undistort_points", "gfo_extract_un", "gfo_extract_stereo_un", "gfo_batch_fetch_un", "gfo_batch_device_view_un",
 ]
 
 
@@ -171,6 +177,12 @@ def load_library():
     L.gfo_extract.argtypes = [vp, vp, i, i, i, vp, vp, i, ip]
     L.gfo_extract_batch.argtypes = [vp, vp, i, i, i, i, vp, vp, i, vp]
     L.gfo_extract_stereo.argtypes = [vp, vp, vp, i, i, i, C.POINTER(StereoParamsC), vp, vp, vp, vp, i, ip, ip, vp, vp, vp, vp, ip]
+    L.gfo_ctx_set_camera.argtypes = [vp, C.POINTER(CameraC), C.POINTER(CameraC)]
+    L.gfo_undistort_points.argtypes = [vp, C.POINTER(CameraC), vp, i, vp]
+    L.gfo_extract_un.argtypes = [vp, vp, i, i, i, vp, vp, vp, i, ip]
+    L.gfo_extract_stereo_un.argtypes = [vp, vp, vp, i, i, i, C.POINTER(StereoParamsC), vp, vp, vp, vp, vp, vp, i, ip, ip, vp, vp, vp, vp, ip]
+    L.gfo_batch_fetch_un.argtypes = [vp, i, vp, i, ip]
+    L.gfo_batch_device_view_un.argtypes = [vp, C.POINTER(vp), ip]
     L.gfo_extract_batch_device.argtypes = [vp, vp, i, i, i, sz, sz]
     L.gfo_batch_counts.argtypes = [vp, vp, vp]
     L.gfo_batch_fetch.argtypes = [vp, i, vp, vp, i, ip]
@@ -226,6 +238,36 @@ def load_library():
     L.gfo_tuning_get.restype = C.c_long
     _lib = L
     return L
+
+
+def make_camera(K, D, R=None, P=None):
+    """gfo_camera from Frame's matrices (any array-likes, converted to float32 as Frame holds them): K 3x3, D with 4, 5 or 8
+    coefficients, R 3x3 or None, P 3x4 (or 3x3) or None.  The library validates the values; only the shapes are checked here."""
+    cam = CameraC()
+    K = np.asarray(K, np.float32).reshape(-1)
+    D = np.asarray(D, np.float32).reshape(-1)
+    if K.size != 9:
+        raise ValueError("K must be 3x3")
+    if D.size > 8:
+        raise ValueError("at most 8 distortion coefficients (12/14-coefficient models are not supported)")
+    cam.K[:] = K.tolist()
+    cam.D[:D.size] = D.tolist()
+    cam.n_dist = int(D.size)
+    if R is not None:
+        R = np.asarray(R, np.float32).reshape(-1)
+        if R.size != 9:
+            raise ValueError("R must be 3x3")
+        cam.R[:] = R.tolist()
+        cam.has_R = 1
+    if P is not None:
+        P = np.asarray(P, np.float32)
+        if P.shape == (3, 3):
+            P = np.concatenate([P, np.zeros((3, 1), np.float32)], axis=1)
+        if P.shape != (3, 4):
+            raise ValueError("P must be 3x4 (or 3x3)")
+        cam.P[:] = P.reshape(-1).tolist()
+        cam.has_P = 1
+    return cam
 
 
 def ptr(a):

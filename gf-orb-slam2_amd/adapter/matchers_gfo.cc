@@ -239,7 +239,9 @@ int Frame::ComputeStereoMatches_Undistorted(bool isOnline)
     gfo_ctx* c = use.c;
     // the two extractors are one stereo rig with this calibration: from the next frame on their two operator() calls go to the
     // device as one stereo submission that also computes this association, and the call below -- on rectified input, where
-    // mvKeysUn == mvKeys -- is answered from it (gfo_ctx_pair: a hint, idempotent, a few nanoseconds when nothing changed)
+    // mvKeysUn == mvKeys -- is answered from it (gfo_ctx_pair: a hint, idempotent, a few nanoseconds when nothing changed).
+    // On a distorted rig the host's mvKeysUn differ from the extracted keypoints and the call is computed as before (the
+    // library can undistort on the device, gfo_ctx_set_camera, but this adapter does not declare the rig's cameras yet)
     if (c && use_r.c) (void)gfo_ctx_pair(c, use_r.c, &p);
     const bool direct = first && !isOnline;    // a fresh frame, offline: the library's arrays are the member's
     std::vector<float> ur, dp;

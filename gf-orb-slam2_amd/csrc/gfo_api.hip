@@ -11,6 +11,7 @@
 
 static std::string g_create_err;
 // live contexts, for gfo_ctx_chain's edges (a destroyed context must disappear from the others' `chain_after`)
+#include <algorithm>
 #include <mutex>
 #include <vector>
 #include <atomic>
@@ -43,7 +44,7 @@ static inline long long align_up(long long v, long long a) { return (v + a - 1) 
 // profiling
 // ---------------------------------------------------------------------------------------------
 static const char* k_stage_names[ST_COUNT] = {"resize", "blur", "fast", "quadtree", "orient_desc",
-                                              "stereo_bucket", "stereo_match", "stereo_cut", "project", "bow"};
+                                              "stereo_bucket", "stereo_match", "stereo_cut", "project", "bow", "undistort"};
 
 static hipEvent_t ev_get(gfo_ctx* c)
 {
@@ -143,13 +144,13 @@ static void free_arena(gfo_ctx* c)
     void* ptrs[] = {c->d_geom, c->d_input, c->d_pyr, c->d_blur, c->d_cand, c->d_cand_cnt, c->d_node_of, c->d_sel,
                     c->d_sel_cnt, c->d_kp, c->d_desc, c->d_kp_cnt, c->d_flags, c->d_xofs, c->d_xcoef, c->d_yofs, c->d_band, c->d_cell_tab, c->d_qt_scratch,
                     c->d_ycoef, c->st.u_right, c->st.depth, c->st.best_dist, c->st.best_idx, c->st.nmatched, c->st.counted,
-                    c->d_scale, c->d_inv_scale, c->st_sort.sx, c->st_sort.sy, c->st_sort.soi, c->st_sort.sdesc, c->st_sort.row_start, c->st_sort.lorder, c->st_sort.lrow_start};
+                    c->d_scale, c->d_inv_scale, c->d_kp_un, c->st_sort.sx, c->st_sort.sy, c->st_sort.soi, c->st_sort.sdesc, c->st_sort.row_start, c->st_sort.lorder, c->st_sort.lrow_start};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     c->d_geom = nullptr; c->d_input = c->d_pyr = c->d_blur = nullptr; c->d_cand = nullptr; c->d_cand_cnt = nullptr;
     c->d_node_of = nullptr; c->d_sel = nullptr; c->d_sel_cnt = nullptr; c->d_kp = nullptr; c->d_desc = nullptr;
     c->d_kp_cnt = nullptr; c->d_flags = nullptr; c->d_xofs = nullptr; c->d_xcoef = nullptr; c->d_yofs = nullptr; c->d_band = nullptr; c->d_cell_tab = nullptr; c->d_od_tab = nullptr; c->od_pairs = 0; c->d_qt_scratch = nullptr;
-    c->d_ycoef = nullptr; c->st = GfoStereoDev{}; c->d_scale = nullptr; c->d_inv_scale = nullptr; c->st_sort = GfoStereoSort{}; c->st_rows_cap = 0;
+    c->d_ycoef = nullptr; c->st = GfoStereoDev{}; c->d_scale = nullptr; c->d_inv_scale = nullptr; c->d_kp_un = nullptr; c->st_sort = GfoStereoSort{}; c->st_rows_cap = 0;
     c->planned = false;
     c->have_batch = c->have_pyramid = c->have_stereo = false;
     c->plan_gen++;                         // every captured launch sequence points into the old arena
@@ -482,6 +483,7 @@ int gfo_plan(gfo_ctx* c, int w, int h, int batch)
     HIP_TRY(c, hipMalloc(&c->d_sel_cnt, B * g.nlevels * sizeof(int)));
     HIP_TRY(c, hipMalloc(&c->d_kp, B * (size_t)g.kp_stride * sizeof(gfo_keypoint)));
     HIP_TRY(c, hipMalloc(&c->d_desc, B * (size_t)g.kp_stride * 32));
+    if (c->has_camera) HIP_TRY(c, hipMalloc(&c->d_kp_un, B * (size_t)g.kp_stride * sizeof(gfo_keypoint)));   // mvKeysUn (gfo_ctx_set_camera)
     HIP_TRY(c, hipMalloc(&c->d_kp_cnt, B * sizeof(int) + 16));   // +16: k_pack_results copies in 16-byte units
     HIP_TRY(c, hipMalloc(&c->d_flags, 8 * sizeof(int)));   // [0..3] the live flags the kernels OR into, [4..7] the snapshot gfo_batch_deliver hands out
     HIP_TRY(c, hipMalloc(&c->d_xofs, xtabv.size() * sizeof(int) + 64));
@@ -605,6 +607,7 @@ extern "C" const char* gfo_last_error(const gfo_ctx* ctx) { return ctx ? ctx->er
 // of every translation unit (hipFuncGetAttributes = load + register, no launch) under one mutex, and later contexts find
 // the device marked.  GFO_PRELOAD=0 restores the lazy behaviour (experiments only).
 static void gfo_kernels_api(std::vector<const void*>& v);
+void (*gfo_kernels_undistort_hook)(std::vector<const void*>& v) = nullptr;
 static std::mutex g_preload_mu;
 static uint64_t g_preloaded_devices = 0;
 static std::atomic<int> g_kernels_preloaded{0};
@@ -616,6 +619,7 @@ static int gfo_preload_kernels(int device)
     std::vector<const void*> ks;
     gfo_kernels_pyramid(ks); gfo_kernels_blur(ks); gfo_kernels_fast(ks); gfo_kernels_quadtree(ks); gfo_kernels_orient_desc(ks);
     gfo_kernels_stereo(ks); gfo_kernels_project(ks); gfo_kernels_bow(ks); gfo_kernels_api(ks);
+    if (gfo_kernels_undistort_hook) gfo_kernels_undistort_hook(ks);
     for (const void* k : ks) {
         hipFuncAttributes fa;
         const hipError_t e = hipFuncGetAttributes(&fa, k);
@@ -708,6 +712,7 @@ extern "C" void gfo_ctx_destroy(gfo_ctx* c)
     if (c->pj.base) (void)hipFree(c->pj.base);
     if (c->d_pj_cand) (void)hipFree(c->d_pj_cand);
     if (c->d_map_desc) (void)hipFree(c->d_map_desc);
+    if (c->d_un_pts) (void)hipFree(c->d_un_pts);
     if (c->side_stream) {
         (void)hipStreamSynchronize(c->side_stream);
         (void)hipStreamDestroy(c->side_stream);
@@ -849,8 +854,9 @@ void gfo_launch_copy16(gfo_ctx* c, void* dst, const void* src, size_t bytes, hip
 static GfoStereoLaunch stereo_batch_launch(gfo_ctx* c, const gfo_stereo_params& p)
 {
     GfoStereoLaunch sl{};
-    sl.kl = c->d_kp; sl.dl = c->d_desc;
-    sl.kr = c->d_kp + c->g.kp_stride; sl.dr = c->d_desc + (size_t)c->g.kp_stride * 32;
+    const gfo_keypoint* kun = gfo_kp_un(c);    // mvKeysUn / mvKeysRightUn (Frame.cc:1205)
+    sl.kl = kun; sl.dl = c->d_desc;
+    sl.kr = kun + c->g.kp_stride; sl.dr = c->d_desc + (size_t)c->g.kp_stride * 32;
     sl.cnt_dev = c->d_kp_cnt; sl.nl_host = 0; sl.nr_host = 0;
     sl.pair_stride_kp = 2LL * c->g.kp_stride; sl.npairs = c->last_nimg / 2;
     sl.d_scale = c->d_scale;
@@ -940,6 +946,9 @@ static int extract_launches(gfo_ctx* c, const GfoInput& in, int nimg, const gfo_
     if (c->launch_err.empty()) gfo_launch_orient_desc(c, in, nimg);
     GFO_PACE_POINT(GFO_STAGE_DESCRIPTORS);
 #undef GFO_PACE_POINT
+    if (c->launch_err.empty() && c->undistort) {    // mvKeysUn next to the keypoints (gfo_ctx_set_camera)
+        if (const int urc = c->undistort(c, nimg)) return urc;
+    }
     if (c->launch_err.empty() && sp) {
         c->last_nimg = nimg;
         GfoStereoLaunch sl = stereo_batch_launch(c, *sp);
@@ -970,7 +979,9 @@ static int extract_launches(gfo_ctx* c, const GfoInput& in, int nimg, const gfo_
 static bool graph_key_eq(const gfo_ctx::GraphKey& a, const gfo_ctx::GraphKey& b)
 {
     return a.base == b.base && a.pack_dst == b.pack_dst && a.pitch == b.pitch && a.img_stride == b.img_stride && a.nimg == b.nimg && a.stereo == b.stereo &&
-           memcmp(&a.sp, &b.sp, sizeof a.sp) == 0 && a.plan_gen == b.plan_gen;
+           memcmp(&a.sp, &b.sp, sizeof a.sp) == 0 && a.plan_gen == b.plan_gen && a.pack_nseg == b.pack_nseg &&
+           std::equal(a.pack_src, a.pack_src + a.pack_nseg, b.pack_src) && std::equal(a.pack_seg_dst, a.pack_seg_dst + a.pack_nseg, b.pack_seg_dst) &&
+           std::equal(a.pack_n16, a.pack_n16 + a.pack_nseg, b.pack_n16);
 }
 
 static int run_extract(gfo_ctx* c, const GfoInput& in, int nimg, const gfo_stereo_params* sp = nullptr, const GfoPack* pack = nullptr)
@@ -984,6 +995,12 @@ static int run_extract(gfo_ctx* c, const GfoInput& in, int nimg, const gfo_stere
         if (sp) key.sp = *sp;
         key.plan_gen = c->plan_gen;
         key.pack_dst = pack ? (const void*)pack->dst[0] : nullptr;
+        key.pack_nseg = pack ? pack->nseg : 0;
+        for (int s_ = 0; s_ < key.pack_nseg; s_++) {
+            key.pack_src[s_] = pack->src[s_];
+            key.pack_seg_dst[s_] = pack->dst[s_];
+            key.pack_n16[s_] = pack->n16[s_];
+        }
         if (c->graph_exec && !graph_key_eq(key, c->graph_key)) {
             (void)hipGraphExecDestroy(c->graph_exec);
             c->graph_exec = nullptr;
@@ -1310,6 +1327,7 @@ int gfo_small_prepare(gfo_ctx* c, int nimg_cap, GfoSmallLayout* L)
     L->o_ds = take(32 * (size_t)ks * nimg_cap);
     L->o_ur = take(4 * (size_t)ks * npair); L->o_dp = take(4 * (size_t)ks * npair); L->o_bd = take(4 * (size_t)ks * npair);
     L->o_bi = take(4 * (size_t)ks * npair); L->o_nm = take(16 * ((npair + 3) / 4));
+    L->o_ku = c->undistort ? take(sizeof(gfo_keypoint) * (size_t)ks * nimg_cap) : 0;
     return gfo_pinned(c, &c->h_out, &c->h_out_bytes, off);
 }
 
@@ -1369,6 +1387,7 @@ int gfo_small_submit(gfo_ctx* c, const GfoSmallLayout& L, int nimg, const gfo_st
     seg(c->d_kp_cnt, L.o_cnt, 4 * (size_t)nimg);          // the count vector is allocated in 16-byte multiples (plan)
     seg(c->d_kp, L.o_kp, sizeof(gfo_keypoint) * (size_t)ks * nimg);
     seg(c->d_desc, L.o_ds, 32 * (size_t)ks * nimg);
+    if (c->pack_kp_un && c->undistort) seg(c->d_kp_un, L.o_ku, sizeof(gfo_keypoint) * (size_t)ks * nimg);
     if (sp) {
         // u_right / depth / nmatched reach the host block from the cut itself, made by the pack kernel's first workgroups
         // (GFO_STEREO_CUT_IN_PACK=0: k_stereo_cut as a launch of its own, then plain copies)
@@ -1495,19 +1514,28 @@ int gfo_small_submit_pairs(gfo_ctx* c, const GfoSmallLayout& L, int npairs, cons
     return GFO_OK;
 }
 
+// kp_un (optional): per image the caller's array for the undistorted keypoints (gfo_extract_un, gfo_extract_stereo_un)
 static int extract_small(gfo_ctx* c, const uint8_t* const* imgs, int nimg, int w, int h, int stride, const gfo_stereo_params* sp,
                          gfo_keypoint* const* kp, uint8_t* const* desc, int cap, int* n, float* u_right, float* depth,
-                         int32_t* best_dist, int32_t* best_idx_r, int* nmatched)
+                         int32_t* best_dist, int32_t* best_idx_r, int* nmatched, gfo_keypoint* const* kp_un = nullptr)
 {
     GfoSmallLayout L;
     int rc = gfo_small_prepare(c, nimg, &L);
     if (rc) return rc;
     rc = gfo_small_upload(c, c, L, 0, nimg, imgs, w, h, stride, c->stream, true);   // a context used on its own (no combiner)
     if (rc) return rc;
+    c->pack_kp_un = kp_un != nullptr;
     rc = gfo_small_submit(c, L, nimg, sp, false);
+    c->pack_kp_un = false;
     if (rc) return rc;
     int over = 0;
     for (int i = 0; i < nimg; i++) over |= gfo_small_collect(c, L, i, kp[i], desc[i], cap, &n[i]);
+    if (kp_un)
+        for (int i = 0; i < nimg; i++) {
+            const int m = n[i] < cap ? n[i] : cap;
+            if (m > 0 && kp_un[i])
+                memcpy(kp_un[i], c->h_out + (c->undistort ? L.o_ku : L.o_kp) + sizeof(gfo_keypoint) * (size_t)c->g.kp_stride * i, sizeof(gfo_keypoint) * (size_t)m);
+        }
     if (sp) gfo_small_collect_stereo(c, L, 0, n[0], cap, u_right, depth, best_dist, best_idx_r, nmatched);
     return over ? fail(c, GFO_ERR_CAPACITY, "an image produced more keypoints than the caller capacity %d", cap) : GFO_OK;
 }
@@ -1522,7 +1550,7 @@ extern "C" int gfo_extract_batch(gfo_ctx* c, const uint8_t* const* imgs, int nim
     }
     if (stride < w) return fail(c, GFO_ERR_INVALID, "stride < width");
     if (cap < 0) return fail(c, GFO_ERR_INVALID, "negative capacity");   // (found by the sanitizer harness of round 6: image i's arrays are kp + i * cap)
-    if (c->combining && nimg == 1) {   // one frame of one caller: may share a device batch with other callers' frames
+    if (c->combining && nimg == 1 && !c->has_camera) {   // one frame of one caller: may share a device batch with other callers' frames
         gfo_keypoint* kps[1] = {kp};
         uint8_t* ds[1] = {desc};
         c->have_batch = c->have_pyramid = c->have_stereo = false;   // the device-side state lives in the combiner's arena
@@ -1566,10 +1594,10 @@ extern "C" int gfo_extract_batch(gfo_ctx* c, const uint8_t* const* imgs, int nim
     return over ? fail(c, GFO_ERR_CAPACITY, "an image produced more keypoints than the caller capacity %d", cap) : GFO_OK;
 }
 
-extern "C" int gfo_extract_stereo(gfo_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int w, int h, int stride,
-                                  const gfo_stereo_params* p, gfo_keypoint* kp_l, uint8_t* desc_l, gfo_keypoint* kp_r,
-                                  uint8_t* desc_r, int cap, int* n_l, int* n_r, float* u_right, float* depth,
-                                  int32_t* best_dist, int32_t* best_idx_r, int* nmatched)
+static int extract_stereo(gfo_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int w, int h, int stride,
+                          const gfo_stereo_params* p, gfo_keypoint* kp_l, uint8_t* desc_l, gfo_keypoint* kp_r,
+                          uint8_t* desc_r, int cap, int* n_l, int* n_r, float* u_right, float* depth,
+                          int32_t* best_dist, int32_t* best_idx_r, int* nmatched, gfo_keypoint* const* kp_un)
 {
     if (!c || !p || !n_l || !n_r || !u_right || !depth || !nmatched) return fail(c, GFO_ERR_INVALID, "bad argument");
     *n_l = *n_r = *nmatched = 0;
@@ -1580,12 +1608,14 @@ extern "C" int gfo_extract_stereo(gfo_ctx* c, const uint8_t* img_l, const uint8_
     gfo_keypoint* kps[2] = {kp_l, kp_r};
     uint8_t* ds[2] = {desc_l, desc_r};
     int n[2] = {0, 0};
-    if (c->combining) {
+    if (c->combining && !c->has_camera) {
         c->have_batch = c->have_pyramid = c->have_stereo = false;
         const int crc = gfo_combined_extract(c, 2, imgs, w, h, stride, p, kps, ds, cap, n, u_right, depth, best_dist, best_idx_r, nmatched);
         if (crc != GFO_COMBINE_DIRECT) {
             *n_l = n[0];
             *n_r = n[1];
+            for (int i = 0; i < 2 && kp_un && (crc == GFO_OK || crc == GFO_ERR_CAPACITY); i++)   // no camera: mvKeysUn == mvKeys
+                if (kps[i] && kp_un[i] && n[i] > 0) memcpy(kp_un[i], kps[i], sizeof(gfo_keypoint) * (size_t)(n[i] < cap ? n[i] : cap));
             return crc;
         }
         n[0] = n[1] = 0;      // the engine cannot serve this frame: alone, below
@@ -1594,10 +1624,86 @@ extern "C" int gfo_extract_stereo(gfo_ctx* c, const uint8_t* img_l, const uint8_
     int rc = gfo_plan(c, w, h, 2);
     if (rc) return rc;
     if (p->n_rows < 1 || p->n_rows > c->st_rows_cap) return fail(c, GFO_ERR_INVALID, "n_rows %d exceeds the planned %d", p->n_rows, c->st_rows_cap);
-    rc = extract_small(c, imgs, 2, w, h, stride, p, kps, ds, cap, n, u_right, depth, best_dist, best_idx_r, nmatched);
+    rc = extract_small(c, imgs, 2, w, h, stride, p, kps, ds, cap, n, u_right, depth, best_dist, best_idx_r, nmatched, kp_un);
     *n_l = n[0];
     *n_r = n[1];
     return rc;
+}
+
+extern "C" int gfo_extract_stereo(gfo_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int w, int h, int stride,
+                                  const gfo_stereo_params* p, gfo_keypoint* kp_l, uint8_t* desc_l, gfo_keypoint* kp_r,
+                                  uint8_t* desc_r, int cap, int* n_l, int* n_r, float* u_right, float* depth,
+                                  int32_t* best_dist, int32_t* best_idx_r, int* nmatched)
+{
+    return extract_stereo(c, img_l, img_r, w, h, stride, p, kp_l, desc_l, kp_r, desc_r, cap, n_l, n_r, u_right, depth, best_dist, best_idx_r,
+                          nmatched, nullptr);
+}
+
+// ---- mvKeysUn (gfo_ctx_set_camera; the undistortion itself is gfo_undistort.hip) -------------------------------------------------
+extern "C" int gfo_extract_stereo_un(gfo_ctx* c, const uint8_t* img_l, const uint8_t* img_r, int w, int h, int stride,
+                                     const gfo_stereo_params* p, gfo_keypoint* kp_l, gfo_keypoint* kp_un_l, uint8_t* desc_l,
+                                     gfo_keypoint* kp_r, gfo_keypoint* kp_un_r, uint8_t* desc_r, int cap, int* n_l, int* n_r,
+                                     float* u_right, float* depth, int32_t* best_dist, int32_t* best_idx_r, int* nmatched)
+{
+    if (cap > 0 && (!kp_un_l || !kp_un_r)) return fail(c, GFO_ERR_INVALID, "bad argument: null undistorted-keypoint array");
+    gfo_keypoint* kun[2] = {kp_un_l, kp_un_r};
+    return extract_stereo(c, img_l, img_r, w, h, stride, p, kp_l, desc_l, kp_r, desc_r, cap, n_l, n_r, u_right, depth, best_dist, best_idx_r,
+                          nmatched, kun);
+}
+
+extern "C" int gfo_extract_un(gfo_ctx* c, const uint8_t* img, int w, int h, int stride, gfo_keypoint* kp, gfo_keypoint* kp_un,
+                              uint8_t* desc, int cap, int* n)
+{
+    if (!c || !n) return GFO_ERR_INVALID;
+    if (!img || w <= 0 || h <= 0) {
+        *n = 0;
+        return GFO_OK;
+    }
+    if (stride < w) return fail(c, GFO_ERR_INVALID, "stride < width");
+    if (cap < 0) return fail(c, GFO_ERR_INVALID, "negative capacity");
+    if (cap > 0 && !kp_un) return fail(c, GFO_ERR_INVALID, "bad argument: null undistorted-keypoint array");
+    if (c->combining && !c->has_camera) {   // no camera: mvKeysUn == mvKeys, and the frame may go through the combiner as gfo_extract's
+        const int rc = gfo_extract(c, img, w, h, stride, kp ? kp : kp_un, desc, cap, n);
+        if (kp && (rc == GFO_OK || rc == GFO_ERR_CAPACITY) && *n > 0) memcpy(kp_un, kp, sizeof(gfo_keypoint) * (size_t)(*n < cap ? *n : cap));
+        return rc;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = gfo_plan(c, w, h, 1);
+    if (rc) return rc;
+    const uint8_t* imgs[1] = {img};
+    gfo_keypoint* kps[1] = {kp};
+    uint8_t* ds[1] = {desc};
+    gfo_keypoint* kun[1] = {kp_un};
+    return extract_small(c, imgs, 1, w, h, stride, nullptr, kps, ds, cap, n, nullptr, nullptr, nullptr, nullptr, nullptr, kun);
+}
+
+extern "C" int gfo_batch_fetch_un(gfo_ctx* c, int image, gfo_keypoint* kp_un, int cap, int* n)
+{
+    if (!c || !n) return GFO_ERR_INVALID;
+    if (!c->have_batch) return fail(c, GFO_ERR_STATE, "no batch has been extracted");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (image < 0 || image >= c->last_nimg) return fail(c, GFO_ERR_INVALID, "image %d out of range", image);
+    if (cap < 0) return fail(c, GFO_ERR_INVALID, "negative capacity");
+    int rc = check_flags(c);
+    if (rc) return rc;
+    int cnt = 0;
+    HIP_TRY(c, hipMemcpyAsync(&cnt, c->d_kp_cnt + image, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n = cnt;
+    const int m = cnt < cap ? cnt : cap;
+    if (m > 0 && kp_un)
+        HIP_TRY(c, hipMemcpyAsync(kp_un, gfo_kp_un(c) + (size_t)image * c->g.kp_stride, sizeof(gfo_keypoint) * m, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return cnt > cap ? fail(c, GFO_ERR_CAPACITY, "%d keypoints, caller capacity %d", cnt, cap) : GFO_OK;
+}
+
+extern "C" int gfo_batch_device_view_un(gfo_ctx* c, const gfo_keypoint** d_kp_un, int* kp_stride)
+{
+    if (!c) return GFO_ERR_INVALID;
+    if (!c->have_batch) return fail(c, GFO_ERR_STATE, "no batch has been extracted");
+    if (d_kp_un) *d_kp_un = gfo_kp_un(c);
+    if (kp_stride) *kp_stride = c->g.kp_stride;
+    return GFO_OK;
 }
 
 extern "C" int gfo_extract(gfo_ctx* c, const uint8_t* img, int w, int h, int stride, gfo_keypoint* kp, uint8_t* desc,
@@ -1713,7 +1819,7 @@ extern "C" int gfo_stereo_match(gfo_ctx* c, const gfo_keypoint* kl, const uint8_
     if (nl == 0) { *nmatched = 0; return GFO_OK; }
     // a declared stereo rig (gfo_ctx_pair) whose last frame these arrays are, bit for bit: the association was computed with that
     // frame (and arrays this library delivered need no validation)
-    if (gfo_has_pair(c) && gfo_pair_lookup(c, kl, dl, nl, kr, dr, nr, sf, nlevels, p, min_d, max_d, u_right, depth, best_dist, best_idx_r, nmatched) == 0)
+    if (!c->has_camera && gfo_has_pair(c) && gfo_pair_lookup(c, kl, dl, nl, kr, dr, nr, sf, nlevels, p, min_d, max_d, u_right, depth, best_dist, best_idx_r, nmatched) == 0)
         return GFO_OK;
     // the kernels index scale[octave] (Frame.h:244, Frame.cc:1204-1206 do the same, unchecked): refuse what would read past it
     for (int i = 0; i < nl; i++)
@@ -1721,7 +1827,7 @@ extern "C" int gfo_stereo_match(gfo_ctx* c, const gfo_keypoint* kl, const uint8_
     for (int i = 0; i < nr; i++)
         if (kr[i].octave < 0 || kr[i].octave >= nlevels) return fail(c, GFO_ERR_INVALID, "right keypoint %d: octave %d outside 0..%d", i, kr[i].octave, nlevels - 1);
     if (p->n_rows < 1 || p->n_rows > 8192) return fail(c, GFO_ERR_INVALID, "n_rows must be 1..8192");
-    if (c->combining) {    // the pairs several threads associate at once share one launch (gfo_combine.hip); 1 = not eligible
+    if (c->combining && !c->has_camera) {    // the pairs several threads associate at once share one launch (gfo_combine.hip); 1 = not eligible
         int status = GFO_OK;
         if (gfo_combined_stereo_match(c, kl, dl, nl, kr, dr, nr, sf, nlevels, p, min_d, max_d, u_right, depth, best_dist, best_idx_r, nmatched, &status) == 0)
             return status;

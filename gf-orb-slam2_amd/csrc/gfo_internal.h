@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/gfo.h"
+#include "../../include/gfo_undistort.h"
 
 // [OCV] build variants (include/gfo.h gfo_build_variant; same values as the checker's ocv_variants.json).  `make EXTRA="-DGFO_OCV_RESIZE=1"`.
 // output rows per wave of the batch-path k_resize / k_resize_tail (k_pyramid.hip)
@@ -198,7 +199,7 @@ struct GfoProjBuf {
 
 enum GfoStage {
     ST_RESIZE = 0, ST_BLUR, ST_FAST, ST_QUADTREE, ST_ORIENT_DESC, ST_STEREO_BUCKET, ST_STEREO, ST_STEREO_CUT,
-    ST_PROJECT, ST_BOW, ST_COUNT
+    ST_PROJECT, ST_BOW, ST_UNDISTORT, ST_COUNT
 };
 
 struct GfoEngine;   // gfo_combine.hip
@@ -300,7 +301,12 @@ struct gfo_ctx {
     uint8_t* h_mout = nullptr; size_t h_mout_bytes = 0;
     bool graph_ok = false;   // GFO_GRAPH=1 opts in (see run_extract)
     hipGraphExec_t graph_exec = nullptr;
-    struct GraphKey { const void* base; const void* pack_dst; long long pitch, img_stride; int nimg, stereo; gfo_stereo_params sp; int plan_gen; } graph_key{};
+    struct GraphKey {
+        const void* base; const void* pack_dst; long long pitch, img_stride; int nimg, stereo; gfo_stereo_params sp; int plan_gen;
+        // the pack kernel's segment list: a per-frame call that returns more arrays (gfo_extract_un: the undistorted keypoints) packs
+        // more segments into the same result block -- a graph captured without them must not be replayed for it
+        int pack_nseg; const void* pack_src[GFO_PACK_MAX]; const void* pack_seg_dst[GFO_PACK_MAX]; int pack_n16[GFO_PACK_MAX];
+    } graph_key{};
     int plan_gen = 0;
     // gfo_batch_deliver: D2H of a batch's results on a stream of its own; the next extraction waits for it before
     // k_orient_desc overwrites the outputs
@@ -316,7 +322,27 @@ struct gfo_ctx {
     void* d_voc = nullptr;
     size_t voc_desc_off = 0, voc_fc_off = 0, voc_nc_off = 0, voc_wid_off = 0, voc_w_off = 0, voc_w64_off = 0;
     int voc_nodes = 0, voc_depth = 0;     // Jacobi rounds of the last gfo_search_by_projection
+    // cameras (gfo_ctx_set_camera, gfo_undistort.hip).  has_camera: one is set -- the context then always takes the direct path (no
+    // combiner, no stereo rig).  undistort != nullptr: the keypoints need the mapping (a camera whose Frame gate does not hold); it is
+    // the launcher gfo_undistort.hip installs, called after the descriptors of every extraction, and writes d_kp_un, which every
+    // consumer standing for mvKeysUn then reads (gfo_kp_un).  (A pointer, not a symbol: the host-code sanitizer build of gfo_api.hip,
+    // tests/host, links no other translation unit.)
+    bool has_camera = false;
+    int (*undistort)(gfo_ctx* c, int nimg) = nullptr;
+    int n_cams = 0;                     // 1: left only (mono gate), 2: left + right (stereo gate)
+    gfo_camera cam_abi[2]{};            // as the caller passed them (setting the same cameras again is a no-op)
+    GfoUndistCam cam[2]{};
+    gfo_keypoint* d_kp_un = nullptr;    // [cap_batch][kp_stride], sized by the launcher
+    size_t kp_un_elems = 0;
+    void* d_un_pts = nullptr;           // gfo_undistort_points: device copy of the caller's points
+    size_t un_pts_bytes = 0;
+    bool pack_kp_un = false;            // the per-frame call in progress returns the undistorted keypoints too (gfo_small_submit)
 };
+
+// what stands for mvKeysUn on the device: the undistorted copy when the context has a camera that needs one, else the keypoints
+inline gfo_keypoint* gfo_kp_un(const gfo_ctx* c) { return c->undistort ? c->d_kp_un : c->d_kp; }
+// gfo_undistort.hip lists its kernels here from a static initialiser (gfo_preload_kernels); nullptr where that file is not linked
+extern void (*gfo_kernels_undistort_hook)(std::vector<const void*>& v);
 
 // ---- kernel launchers (each in its own .hip file) ------------------------------------------
 // the candidate-counter pointer for the first pyramid launch of an extraction (nullptr afterwards)
@@ -412,6 +438,7 @@ struct GfoSmallLayout {
     int pitch;            // of the staged images: the width when that keeps rows 16-byte aligned (one memcpy / one DMA per image), else the arena's
     size_t img_bytes;
     size_t o_fl, o_cnt, o_kp, o_ds, o_ur, o_dp, o_bd, o_bi, o_nm;   // offsets into the pinned result buffer
+    size_t o_ku;          // the undistorted keypoints (contexts with a camera only, gfo_ctx::pack_kp_un)
 };
 int gfo_small_prepare(gfo_ctx* c, int nimg_cap, GfoSmallLayout* L);
 int gfo_small_upload(gfo_ctx* c, gfo_ctx* ec, const GfoSmallLayout& L, int first, int count, const uint8_t* const* imgs, int w, int h, int stride,

@@ -1790,7 +1790,7 @@ extern "C" int gfo_search_by_projection_batch(gfo_ctx* c, const gfo_projection_b
     }
     ProjB a{};
     const int step = p->stereo ? 2 : 1;   // stereo: frame k = left image 2k
-    a.kp = c->d_kp; a.kp_stride = (long long)step * ks;
+    a.kp = gfo_kp_un(c); a.kp_stride = (long long)step * ks;   // mvKeysUn: the undistorted copy when the context has a camera
     a.desc = c->d_desc;
     a.u_right = p->stereo ? c->st.u_right : nullptr; a.ur_stride = ks;
     a.taken0 = d_taken; a.tk_stride = ks;

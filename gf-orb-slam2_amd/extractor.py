@@ -160,6 +160,98 @@ class ORBextractor:
         a, b = nl.value, nr.value
         return kl[:a].copy(), dl[:a].copy(), kr[:b].copy(), dr[:b].copy(), nm.value, u[:a].copy(), dp[:a].copy(), bd[:a].copy(), bi[:a].copy()
 
+    # mvKeysUn: Frame::UndistortKeyPoints / UndistortKeyPointsStereo (Frame.cc:670-756) on the device (gfo_ctx_set_camera)
+    def set_camera(self, K, D=None, R=None, P=None, right=None):
+        """The camera(s) of this extractor's images: `K`, `D` (4, 5 or 8 coefficients), optional `R` (3x3) and `P` (3x4), as Frame holds
+        them; `right` = (K, D[, R[, P]]) or a dict of those for the right camera of a stereo pair (images 2k + 1 of a batch).  From then
+        on every extraction also computes mvKeysUn, and the association / projection chains read it.  K=None clears the cameras.
+        Without `right`, a camera without P is projected with P = K (Frame::UndistortKeyPoints); an R given there is applied."""
+        from ._lib import make_camera
+        if K is None:
+            if right is not None:
+                raise ValueError("a right camera without a left one")
+            check(self._L, self._ctx, self._L.gfo_ctx_set_camera(self._ctx, None, None))
+            return
+        if D is None:
+            raise ValueError("set_camera(K, D, ...): the distortion coefficients D (4, 5 or 8 values) are required; set_camera(None) clears")
+        left = make_camera(K, D, R, P)
+        rc = None
+        if right is not None:
+            rc = make_camera(**right) if isinstance(right, dict) else make_camera(*right)
+        check(self._L, self._ctx, self._L.gfo_ctx_set_camera(self._ctx, C.byref(left), C.byref(rc) if rc is not None else None))
+
+    def undistort_points(self, xy, K, D, R=None, P=None):
+        """cv::undistortPoints(xy, K, D, R, P) on the device (gfo_undistort_points; no Frame gate): (n, 2) float32 -> (n, 2) float32"""
+        from ._lib import make_camera
+        cam = make_camera(K, D, R, P)
+        xy = np.ascontiguousarray(np.asarray(xy, np.float32).reshape(-1, 2))
+        out = np.zeros_like(xy)
+        check(self._L, self._ctx, self._L.gfo_undistort_points(self._ctx, C.byref(cam), ptr(xy), len(xy), ptr(out)))
+        return out
+
+    def extract_un(self, image):
+        """operator() + mvKeysUn (gfo_extract_un): (keypoints, undistorted keypoints, descriptors)"""
+        image = np.ascontiguousarray(image, np.uint8)
+        h, w = image.shape
+        cap = max(self.max_keypoints(), self.nfeatures + 64)
+        while True:
+            kp = np.zeros(cap, KEYPOINT_DTYPE)
+            ku = np.zeros(cap, KEYPOINT_DTYPE)
+            desc = np.zeros((cap, 32), np.uint8)
+            n = C.c_int()
+            rc = self._L.gfo_extract_un(self._ctx, ptr(image), w, h, w, ptr(kp), ptr(ku), ptr(desc), cap, C.byref(n))
+            if rc == -3:
+                cap = max(n.value, self.max_keypoints())
+                continue
+            check(self._L, self._ctx, rc)
+            break
+        self._last_shape = (h, w)
+        m = n.value
+        return kp[:m].copy(), ku[:m].copy(), desc[:m].copy()
+
+    def extract_stereo_un(self, left, right, params):
+        """extract_stereo + mvKeysUn / mvKeysRightUn (gfo_extract_stereo_un); the association ran on the undistorted arrays.
+        Returns (kp_l, kp_un_l, desc_l, kp_r, kp_un_r, desc_r, nmatched, mvuRight, mvDepth, best_dist, best_idx_r)."""
+        from ._lib import StereoParamsC
+        left = np.ascontiguousarray(left, np.uint8)
+        right = np.ascontiguousarray(right, np.uint8)
+        h, w = left.shape
+        assert right.shape == (h, w)
+        cap = max(self.max_keypoints(), self.nfeatures + 64)
+        p = StereoParamsC(*params)
+        while True:
+            kl = np.zeros(cap, KEYPOINT_DTYPE); kr = np.zeros(cap, KEYPOINT_DTYPE)
+            ul = np.zeros(cap, KEYPOINT_DTYPE); ur = np.zeros(cap, KEYPOINT_DTYPE)
+            dl = np.zeros((cap, 32), np.uint8); dr = np.zeros((cap, 32), np.uint8)
+            u = np.zeros(cap, np.float32); dp = np.zeros(cap, np.float32)
+            bd = np.zeros(cap, np.int32); bi = np.zeros(cap, np.int32)
+            nl, nr, nm = C.c_int(), C.c_int(), C.c_int()
+            rc = self._L.gfo_extract_stereo_un(self._ctx, ptr(left), ptr(right), w, h, w, C.byref(p), ptr(kl), ptr(ul), ptr(dl), ptr(kr), ptr(ur),
+                                               ptr(dr), cap, C.byref(nl), C.byref(nr), ptr(u), ptr(dp), ptr(bd), ptr(bi), C.byref(nm))
+            if rc == -3:
+                cap = max(nl.value, nr.value, self.max_keypoints())
+                continue
+            check(self._L, self._ctx, rc)
+            break
+        self._last_shape = (h, w)
+        a, b = nl.value, nr.value
+        return (kl[:a].copy(), ul[:a].copy(), dl[:a].copy(), kr[:b].copy(), ur[:b].copy(), dr[:b].copy(), nm.value, u[:a].copy(), dp[:a].copy(),
+                bd[:a].copy(), bi[:a].copy())
+
+    def batch_fetch_un(self, image):
+        """mvKeysUn of image `image` of the last batch (gfo_batch_fetch_un; the keypoints themselves without a camera)"""
+        cap = self.max_keypoints()
+        ku = np.zeros(cap, KEYPOINT_DTYPE)
+        n = C.c_int()
+        check(self._L, self._ctx, self._L.gfo_batch_fetch_un(self._ctx, image, ptr(ku), cap, C.byref(n)))
+        return ku[:n.value].copy()
+
+    def batch_device_view_un(self):
+        """(device address of the batch's undistorted keypoints, kp_stride) -- gfo_batch_device_view_un"""
+        d, ks = C.c_void_p(), C.c_int()
+        check(self._L, self._ctx, self._L.gfo_batch_device_view_un(self._ctx, C.byref(d), C.byref(ks)))
+        return d.value, ks.value
+
     # device-resident path (bench / chained stereo)
     def extract_batch_device(self, dev_ptr, nimg, w, h, pitch=None, img_stride=None):
         pitch = pitch or w

@@ -206,13 +206,56 @@ int gfo_stereo_match_batch(gfo_ctx* ctx, const gfo_stereo_params* p);
 /* One stereo frame in ONE submission: the body of the reference's stereo Frame constructor --
  * ExtractORB(0, imLeft) and ExtractORB(1, imRight) on two threads (src/Frame.cc:84-87, 478-484), then
  * ComputeStereoMatches_Undistorted (:100, 1167-1316) -- as one H2D copy of both images, one replay of the captured
- * launch sequence (both extractions + the association), one D2H burst and one synchronisation.  The extracted
- * keypoints stand for mvKeysUn / mvKeysRightUn (rectified input, as the reference's stereo examples provide).
+ * launch sequence (both extractions + the association), one D2H burst and one synchronisation.  The association runs on
+ * mvKeysUn / mvKeysRightUn: the extracted keypoints themselves when the context has no camera (rectified or distortion-free
+ * input), their undistorted copies when it has one (gfo_ctx_set_camera; gfo_extract_stereo_un also returns those copies).
  * kp/desc buffers take `cap` entries per image; u_right/depth/best_dist/best_idx_r take cap entries (left keypoints). */
 int gfo_extract_stereo(gfo_ctx* ctx, const uint8_t* img_l, const uint8_t* img_r, int w, int h, int stride,
                        const gfo_stereo_params* p, gfo_keypoint* kp_l, uint8_t* desc_l, gfo_keypoint* kp_r,
                        uint8_t* desc_r, int cap, int* n_l, int* n_r, float* u_right, float* depth,
                        int32_t* best_dist, int32_t* best_idx_r, int* nmatched);
+
+/* Keypoint undistortion: Frame::UndistortKeyPoints / UndistortKeyPointsStereo (src/Frame.cc:670-756) = cv::undistortPoints(pts, K, D, R, P)
+ * of OpenCV 3.4.1 (radial-tangential model; include/gfo_undistort.h, DESIGN.md 0 [OCV]), on the device.
+ * gfo_camera holds the matrices exactly as Frame holds them (float, row-major): K 3x3, D = k1 k2 p1 p2 [k3 [k4 k5 k6]] (n_dist 4, 5
+ * or 8), R 3x3 when has_R, P 3x4 when has_P (only its left 3x3 is used).  Fisheye and 12/14-coefficient models are refused.
+ *
+ * gfo_ctx_set_camera(ctx, left, right): `left` is the camera of single-image calls and of images 2k of a batch, `right` (may be NULL)
+ * that of images 2k + 1 -- the pair convention of gfo_stereo_match_batch.  From then on every extraction of the context also writes
+ * the undistorted copy of its keypoints (mvKeysUn: same size, angle, response, octave, class_id; only x, y change) next to the raw
+ * ones, and every device consumer that stands for mvKeysUn reads the copy: the association of gfo_extract_stereo /
+ * gfo_stereo_match_batch and gfo_search_by_projection_batch, grid included.  Raw keypoints and descriptors are unchanged (extraction
+ * runs on the raw image).  The Frame gates apply: with `right` given, a left camera with k1 == 0 leaves BOTH sides unchanged
+ * (Frame.cc:672-677); without it, k1 == 0 leaves the keypoints unchanged (:726-730), and a camera without P is projected with P = K
+ * (UndistortKeyPoints passes mK as P and no R, :740; an R the caller gives is still applied: RR = K * R).  NULL, NULL clears the cameras; setting the
+ * cameras the context already has is a no-op.  Everything is validated first (finite values, fx, fy != 0, n_dist in {4, 5, 8},
+ * has_R / has_P 0 or 1): a refused call returns GFO_ERR_INVALID and leaves the context as it was.
+ * Limitation: a context with a camera always takes the direct path -- its calls never enter the frame combiner
+ * (gfo_ctx_set_combining) and never meet a partner of a stereo rig (gfo_ctx_pair); results are those of the direct call. */
+typedef struct {
+    float K[9];
+    float D[8];
+    int32_t n_dist;
+    float R[9];
+    float P[12];
+    int32_t has_R, has_P;
+} gfo_camera;
+int gfo_ctx_set_camera(gfo_ctx* ctx, const gfo_camera* left, const gfo_camera* right);
+/* cv::undistortPoints(xy, K, D, R, P) on n arbitrary (x, y) float pairs through the same device code (no Frame gate: the caller's, as in
+ * Frame::ComputeImageBounds / ComputeImageBoundsStereo, src/Frame.cc:760-830).  out_xy may equal xy.  Synchronous; n = 0 is a no-op. */
+int gfo_undistort_points(gfo_ctx* ctx, const gfo_camera* cam, const float* xy, int n, float* out_xy);
+/* gfo_extract + the undistorted copy of the keypoints (kp_un, cap entries; equal to kp when the context has no camera or the gate holds). */
+int gfo_extract_un(gfo_ctx* ctx, const uint8_t* img, int w, int h, int stride, gfo_keypoint* kp, gfo_keypoint* kp_un, uint8_t* desc,
+                   int cap, int* n);
+/* gfo_extract_stereo + mvKeysUn / mvKeysRightUn (kp_un_l, kp_un_r: cap entries each); the association ran on those arrays. */
+int gfo_extract_stereo_un(gfo_ctx* ctx, const uint8_t* img_l, const uint8_t* img_r, int w, int h, int stride,
+                          const gfo_stereo_params* p, gfo_keypoint* kp_l, gfo_keypoint* kp_un_l, uint8_t* desc_l, gfo_keypoint* kp_r,
+                          gfo_keypoint* kp_un_r, uint8_t* desc_r, int cap, int* n_l, int* n_r, float* u_right, float* depth,
+                          int32_t* best_dist, int32_t* best_idx_r, int* nmatched);
+/* gfo_batch_fetch of the undistorted keypoints of image `image` of the last batch (the raw ones without a camera) */
+int gfo_batch_fetch_un(gfo_ctx* ctx, int image, gfo_keypoint* kp_un, int cap, int* n);
+/* device address of the batch's undistorted keypoints, [nimg][kp_stride] as gfo_batch_device_views (d_kp itself without a camera) */
+int gfo_batch_device_view_un(gfo_ctx* ctx, const gfo_keypoint** d_kp_un, int* kp_stride);
 
 /* Frame::ComputeStereoMatches (src/Frame.cc:889-1078): the SAD sub-pixel variant the reference compiles out
  * with ALTER_STEREO_MATCHING (include/Frame.h:38).  It reads pyramid pixels of BOTH cameras, so it exists in the
@@ -375,8 +418,9 @@ int gfo_search_for_fusion(gfo_ctx* ctx, const gfo_keypoint* kp_un, const uint8_t
  * until replaced by the next upload.  The host buffer is free on return.
  * gfo_search_by_projection_batch: one search per frame of the last batch.  mps is [frames][m]: the per-frame
  * projection of every map point (Frame::isInFrustum fills mTrackProjX/Y/XR, mnTrackScaleLevel, mTrackViewCos,
- * mbTrackInView per frame, Frame.cc:512-590).  The extractor's keypoints stand for mvKeysUn (rectified or
- * distortion-free input); bounds = mnMinX..mnMaxY.  stereo = 1: frame k is the pair k of the last
+ * mbTrackInView per frame, Frame.cc:512-590).  The keypoints searched are mvKeysUn: the extractor's own when the context
+ * has no camera (rectified or distortion-free input), their undistorted copies when it has one (gfo_ctx_set_camera), grid
+ * included; bounds = mnMinX..mnMaxY.  stereo = 1: frame k is the pair k of the last
  * gfo_stereo_match_batch (left keypoints + mvuRight), otherwise frame k = image k with mvuRight = -1.
  * on_device = 1: mps / kp_taken are device pointers used in place (they must stay valid until the stream has
  * consumed them); 0: host arrays, copied.  kp_taken (optional) is [frames][kp_stride] with kp_stride from
