@@ -6,11 +6,12 @@
  * PARITY STATUS: "parity unpinned" at the OpenCV boundary.  The reference's CPU extractor
  * calls OpenCV 3.4.1 (cv::FAST, cv::resize, cv::GaussianBlur, cv::fastAtan2, cvRound), which
  * is neither vendored in /root/reference nor installed in this image, and the reference's
- * tests hold no golden keypoints/descriptors.  Everything that lives
- * in the reference's own sources (cell grid, quadtree, angle, descriptor, matchers) follows
- * the cited lines; the OpenCV pieces restate the published 3.4.x algorithms from memory.
- * The only known answers this oracle is pinned against are the level geometry / quotas /
- * umax table of SURVEY.md 8 and the popcount definition of DescriptorDistance.
+ * tests hold no golden keypoints/descriptors; the OpenCV pieces restate
+ * the published 3.4.x algorithms from memory.  The extractor logic that lives in the
+ * reference's own sources (tables, pyramid frame, cell grid, quadtree, angle, descriptor) is
+ * pinned: oracle/_ref/libref_orbextractor*.so run src/ORBextractor.cc itself on these [OCV]
+ * primitives, and tests/test_reference_extractor.py compares bit for bit.
+ * The matchers follow the cited lines; DescriptorDistance is pinned by its popcount definition.
  */
 #ifndef ORB_ORACLE_H
 #define ORB_ORACLE_H

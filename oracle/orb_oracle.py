@@ -630,8 +630,9 @@ REFERENCE_ROOT = os.environ.get("GFO_REFERENCE_ROOT", "/root/reference")
 
 
 def build_ref():
-    """oracle/_ref/libdbow2_fold.so from the reference's own DBoW2 BowVector.cpp / FeatureVector.cpp, compiled unmodified where they
-    lie (oracle/Makefile, target ref).  Only where the reference tree exists (the build container); returns the path or None."""
+    """oracle/_ref/: libdbow2_fold.so from the reference's own DBoW2 BowVector.cpp / FeatureVector.cpp, and libref_orbextractor.so /
+    libref_orbextractor_fma.so from its src/ORBextractor.cc, all compiled unmodified where they lie (oracle/Makefile, target ref).
+    Only where the reference tree exists (the build container); returns the fold library's path or None."""
     if not os.path.exists(os.path.join(REFERENCE_ROOT, "Thirdparty", "DBoW2", "DBoW2", "BowVector.cpp")):
         return _REF_FOLD if os.path.exists(_REF_FOLD) else None
     subprocess.check_call(["make", "-C", _HERE, "-s", "ref", f"REFERENCE={REFERENCE_ROOT}"])
@@ -653,6 +654,154 @@ def ref_bow_fold(word, weight, node, weighting=0, norm=1):
             raise FileNotFoundError(_REF_FOLD)
         _ref_lib = C.CDLL(_REF_FOLD)
     return _fold(_ref_lib.ref_bow_fold, word, weight, node, weighting, norm)
+
+
+# ---- the reference's own ORBextractor.cc (oracle/_ref/libref_orbextractor*.so, ref_shim/orbextractor_shim.cc) -------------------
+# Two builds of the same unmodified file; each is compared with the oracle variant that states its arithmetic (oracle/Makefile):
+REF_EXTRACTOR_BUILDS = {"unfused": ("libref_orbextractor.so", TRIG_LIBM, ROT_UNFUSED),    # -ffp-contract=off
+                        "fma": ("libref_orbextractor_fma.so", TRIG_LIBM, ROT_FMA)}           # -O3, contraction on (the reference's own)
+# what the libraries are built from: a library older than one of these is stale
+REF_EXTRACTOR_SOURCES = [os.path.join(_HERE, f) for f in ("ref_shim/orbextractor_shim.cc", "ref_shim/cv_arith.cc", "ref_shim/cv_arith.h",
+                                                           "ref_shim/ref_exports.map", "orb_oracle.h", "Makefile")] + \
+                        [os.path.join(_HERE, "..", "tests", "cv_standin", "opencv", "cv.h")]
+
+
+class RefExtractorError(RuntimeError):
+    """The reference's extractor threw (rc -1: a vector sized from a negative node count), its arena ran out (rc -2), or the call was
+    refused because the reference would index an empty node vector (rc -4: undefined behaviour, orbextractor_shim.cc)."""
+
+
+def ref_extractor_path(build="unfused"):
+    return os.path.join(_REF_DIR, REF_EXTRACTOR_BUILDS[build][0])
+
+
+def ref_extractor_stale(build="unfused"):
+    """the sources newer than the built library (the reference's own ORBextractor.cc included where the tree exists)"""
+    path = ref_extractor_path(build)
+    srcs = REF_EXTRACTOR_SOURCES + [os.path.join(REFERENCE_ROOT, "src", "ORBextractor.cc"), os.path.join(REFERENCE_ROOT, "include", "ORBextractor.h")]
+    t = os.path.getmtime(path)
+    return [f for f in srcs if os.path.exists(f) and os.path.getmtime(f) > t]
+
+
+_ref_ex_libs = {}
+
+
+def ref_extractor_lib(build="unfused"):
+    if build not in _ref_ex_libs:
+        path = ref_extractor_path(build)
+        if not os.path.exists(path):
+            raise FileNotFoundError(path)
+        lib()      # the oracle first: the reference build's liborb_oracle.so ($ORIGIN/..) is then this same loaded copy, [OCV] switches and all
+        L = C.CDLL(path)
+        vp, i = C.c_void_p, C.c_int
+        L.ref_ex_create.restype = vp
+        L.ref_ex_create.argtypes = [i, C.c_float, i, i, i]
+        L.ref_ex_destroy.argtypes = [vp]
+        L.ref_ex_tables.argtypes = [vp] + [vp] * 7
+        L.ref_ex_extract.argtypes = [vp, vp, i, i, i]
+        L.ref_ex_result.argtypes = [vp, vp, vp]
+        L.ref_ex_compute_pyramid.argtypes = [vp, vp, i, i, i]
+        L.ref_ex_level_size.argtypes = [vp, i, C.POINTER(i), C.POINTER(i)]
+        L.ref_ex_get_level.argtypes = [vp, i, i, vp, i]
+        L.ref_fast_log_get.argtypes = [vp, vp]
+        L.ref_set_system_allocator.argtypes = [i]
+        L.ref_arena_stats.argtypes = [vp]
+        L.ref_list_node_size.restype = C.c_longlong
+        _ref_ex_libs[build] = L
+    return _ref_ex_libs[build]
+
+
+FAST_CALL_DTYPE = np.dtype([("level_w", "<i4"), ("level_h", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"),
+                            ("threshold", "<i4"), ("first", "<i4"), ("count", "<i4")])
+
+
+class RefExtractor:
+    """The reference's ORB_SLAM2::ORBextractor itself (ORBextractor.cc compiled unmodified), with OpenCV's arithmetic routed to this
+    oracle's [OCV] primitives.  Same interface as OracleExtractor where the two overlap."""
+
+    def __init__(self, nfeatures=2000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, build="unfused"):
+        self._L = ref_extractor_lib(build)
+        self._h = self._L.ref_ex_create(nfeatures, scale_factor, nlevels, ini_th, min_th)
+        if not self._h:
+            raise ValueError("ref_ex_create failed")
+        self.nfeatures, self.nlevels, self.build = nfeatures, nlevels, build
+        self._scale_factor_arg, self._ini, self._min = scale_factor, ini_th, min_th
+        self.trig, self.rot = REF_EXTRACTOR_BUILDS[build][1:]
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.ref_ex_destroy(self._h)
+            self._h = None
+
+    def tables(self):
+        n = self.nlevels
+        t = {k: np.zeros(n, np.float32) for k in ("scale_factors", "inv_scale_factors", "level_sigma2", "inv_level_sigma2")}
+        t["features_per_level"] = np.zeros(n, np.int32)
+        t["umax"] = np.zeros(16, np.int32)
+        t["pattern"] = np.zeros((512, 2), np.int32)
+        self._L.ref_ex_tables(self._h, *[_p(t[k]) for k in ("scale_factors", "inv_scale_factors", "level_sigma2", "inv_level_sigma2",
+                                                            "features_per_level", "umax", "pattern")])
+        return t
+
+    def __call__(self, image):
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        h, w = image.shape
+        n = self._L.ref_ex_extract(self._h, _p(image) if image.size else None, w, h, w)
+        if n < 0:
+            raise RefExtractorError(f"ORBextractor::operator() failed (rc {n}) on a {w}x{h} image")
+        kp = np.zeros(max(n, 1), dtype=KEYPOINT_DTYPE)
+        desc = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        self._L.ref_ex_result(self._h, _p(kp), _p(desc))
+        return kp[:n].copy(), desc[:n].copy()
+
+    def compute_pyramid(self, image):
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        h, w = image.shape
+        rc = self._L.ref_ex_compute_pyramid(self._h, _p(image) if image.size else None, w, h, w)
+        if rc != 0:
+            raise RefExtractorError(f"ORBextractor::ComputePyramid failed (rc {rc}) on a {w}x{h} image")
+
+    def level_size(self, level):
+        w, h = C.c_int(), C.c_int()
+        if self._L.ref_ex_level_size(self._h, level, C.byref(w), C.byref(h)) != 0:
+            raise IndexError(level)
+        return w.value, h.value
+
+    def level(self, level, padded=False):
+        """mvImagePyramid[level] of the last call (unblurred); padded: with the 19-px frame ComputePyramid wrote around it"""
+        w, h = self.level_size(level)
+        if padded:
+            w, h = w + 38, h + 38
+        out = np.zeros((h, w), dtype=np.uint8)
+        if self._L.ref_ex_get_level(self._h, level, 1 if padded else 0, _p(out), w) != 0:
+            raise IndexError(level)
+        return out
+
+    def fast_log(self):
+        """every cv::FAST call of the last call, in order: FAST_CALL_DTYPE records, and the {x, y, score} corners they returned
+        (relative to the ROI; record r's are corners[r.first : r.first + r.count])"""
+        L = self._L
+        calls = np.zeros(max(L.ref_fast_log_size(), 1), FAST_CALL_DTYPE)
+        corners = np.zeros((max(L.ref_fast_log_ncorners(), 1), 3), np.int32)
+        L.ref_fast_log_get(_p(calls), _p(corners))
+        return calls[:L.ref_fast_log_size()], corners[:L.ref_fast_log_ncorners()]
+
+    def arena_stats(self):
+        """of the last call: arena allocations, std::list<ExtractorNode> node allocations, malloc allocations, arena bytes, overflows"""
+        out = np.zeros(5, np.int64)
+        self._L.ref_arena_stats(_p(out))
+        return dict(zip(("arena", "list_nodes", "malloc", "bytes", "overflows"), (int(x) for x in out)))
+
+    def oracle(self):
+        """the OracleExtractor with the same parameters and the trig / rotation variant that states this build's arithmetic"""
+        o = OracleExtractor(self.nfeatures, self._scale_factor_arg, self.nlevels, self._ini, self._min)
+        o.set_variant(self.trig, self.rot)
+        return o
+
+
+def ref_set_system_allocator(on, build="unfused"):
+    """1: the reference's allocations go to malloc / free during a call (glibc reuses freed list nodes); 0: the bump arena (default)"""
+    ref_extractor_lib(build).ref_set_system_allocator(1 if on else 0)
 
 
 class ProjMode(C.Structure):

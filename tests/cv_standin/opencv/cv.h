@@ -6,10 +6,15 @@
 //     reference-counted storage shared by copies and views, create() that keeps a matching allocation, ROI / row / col
 //     views, clone(), copyTo() into a view, at<T>(), and small CV_32F matrix arithmetic (the host-side projections the
 //     matcher adapters do with the reference's own expressions).
-// It is NOT OpenCV and pins nothing about OpenCV's arithmetic: no resize, blur, FAST or fastAtan2 lives here, no reference
-// SOURCE file is compiled with it, the oracle does not use it, and libgfo.so never sees it (plain pointers cross the C ABI).
+//   * oracle/_ref/libref_orbextractor*.so compile the reference's src/ORBextractor.cc, unmodified, against it; the OpenCV
+//     arithmetic that file calls (FAST, resize, GaussianBlur, copyMakeBorder, fastAtan2, cvFloor / cvCeil) is declared and
+//     forwarded to the oracle's [OCV] primitives by oracle/ref_shim/cv_arith.h, not here.  Mat::zeros is a deferred initialiser
+//     because computeDescriptors (ORBextractor.cc:1105) assigns it to a row-range view of its output and relies on the in-place fill.
+// It is NOT OpenCV and pins nothing about OpenCV's arithmetic: no resize, blur, FAST or fastAtan2 lives here, and libgfo.so never
+// sees it (plain pointers cross the C ABI).
 #pragma once
 #include <algorithm>
+#include <cassert>
 #include <climits>
 #include <cmath>
 #include <cstddef>
@@ -29,6 +34,9 @@
 #define CV_8UC1 0
 #define CV_32F 5
 #define CV_64F 6
+#define CV_PI 3.1415926535897932384626433832795
+
+typedef unsigned char uchar;
 
 namespace cv
 {
@@ -37,6 +45,13 @@ template <class T> struct Point_ { T x, y; Point_() : x(0), y(0) {} Point_(T a, 
 typedef Point_<int> Point2i;
 typedef Point2i Point;
 typedef Point_<float> Point2f;
+// Point_ *= float as OpenCV 3.4 states it (saturate_cast<T>(a.x * b)), for the floating-point points the reference scales
+inline Point_<float>& operator*=(Point_<float>& a, float b) { a.x = a.x * b; a.y = a.y * b; return a; }
+inline Point_<double>& operator*=(Point_<double>& a, float b) { a.x = a.x * b; a.y = a.y * b; return a; }
+struct Size { int width, height; Size() : width(0), height(0) {} Size(int w, int h) : width(w), height(h) {} };
+enum { BORDER_CONSTANT = 0, BORDER_REPLICATE = 1, BORDER_REFLECT = 2, BORDER_WRAP = 3, BORDER_REFLECT_101 = 4, BORDER_DEFAULT = 4,
+       BORDER_ISOLATED = 16 };
+enum { INTER_NEAREST = 0, INTER_LINEAR = 1, INTER_CUBIC = 2, INTER_AREA = 3 };
 struct Rect { int x, y, width, height; Rect(int a, int b, int c, int d) : x(a), y(b), width(c), height(d) {} };
 struct Scalar { double v; Scalar(double a = 0) : v(a) {} };
 struct KeyPoint {
@@ -46,6 +61,11 @@ struct KeyPoint {
 };
 
 class _OutputArray;
+class Mat;
+
+// what Mat::zeros returns: a deferred initialiser.  As in OpenCV, assigning it to a Mat of the same size and type zero-fills that Mat
+// IN PLACE (a row-range view stays a view of its parent); a Mat constructed from it is a new zeroed allocation.
+struct MatExpr { int rows, cols, type; };
 
 class Mat
 {
@@ -56,6 +76,14 @@ public:
     Mat() : data(NULL), rows(0), cols(0), step(0), type_(CV_8U) {}
     Mat(int r, int c, int type) : data(NULL), rows(0), cols(0), step(0), type_(CV_8U) { create(r, c, type); }
     Mat(int r, int c, int type, const Scalar& s) : data(NULL), rows(0), cols(0), step(0), type_(CV_8U) { create(r, c, type); fill(s.v); }
+    Mat(Size sz, int type) : data(NULL), rows(0), cols(0), step(0), type_(CV_8U) { create(sz.height, sz.width, type); }
+    Mat(const MatExpr& e) : data(NULL), rows(0), cols(0), step(0), type_(CV_8U) { create(e.rows, e.cols, e.type); }
+    Mat& operator=(const MatExpr& e)
+    {
+        create(e.rows, e.cols, e.type);
+        for (int i = 0; i < rows; i++) memset(data + (size_t)i * step, 0, (size_t)cols * esz(type_));
+        return *this;
+    }
     // user-owned memory (what cv::Mat(rows, cols, type, ptr, step) is): a header, nothing allocated
     Mat(int r, int c, int type, void* p, size_t st = 0) : data((unsigned char*)p), rows(r), cols(c), step(st ? st : (size_t)c * esz(type)), type_(type) {}
     // copies and views share the allocation (shared_ptr = the reference count)
@@ -76,6 +104,19 @@ public:
     template <class T> const T& at(int i, int j) const { return const_cast<Mat*>(this)->at<T>(i, j); }
     template <class T> T* ptr(int i = 0) { return reinterpret_cast<T*>(data + (size_t)i * step); }
     template <class T> const T* ptr(int i = 0) const { return reinterpret_cast<const T*>(data + (size_t)i * step); }
+    uchar* ptr(int i = 0) { return data + (size_t)i * step; }
+    const uchar* ptr(int i = 0) const { return data + (size_t)i * step; }
+    size_t step1() const { return step / esz(type_); }     // (single-channel types: elemSize1 == elemSize)
+    Size size() const { return Size(cols, rows); }
+    // where a view lies in the allocation it shares (what OpenCV's datastart / dataend give); user memory is its own whole
+    void locateROI(Size& whole, Point& ofs) const
+    {
+        if (!store || !data || step == 0) { whole = size(); ofs = Point(0, 0); return; }
+        const size_t off = (size_t)(data - store->data());
+        whole = Size((int)(step / esz(type_)), (int)((store->size() - 8) / step));
+        ofs = Point((int)(off % step / esz(type_)), (int)(off / step));
+    }
+    bool isSubmatrix() const { Size w; Point o; locateROI(w, o); return w.width != cols || w.height != rows; }
     Mat clone() const
     {
         Mat m;
@@ -109,7 +150,7 @@ public:
     inline void copyTo(const _OutputArray& dst) const;
     bool isContinuous() const { return rows <= 1 || step == (size_t)cols * esz(type_); }
     void release() { store.reset(); data = NULL; rows = cols = 0; step = 0; }
-    static Mat zeros(int r, int c, int t) { return Mat(r, c, t); }
+    static MatExpr zeros(int r, int c, int t) { MatExpr e = {r, c, t}; return e; }
     static Mat eye(int r, int c, int t)
     {
         Mat m(r, c, t);
